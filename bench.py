@@ -19,6 +19,13 @@ time); `roofline` = the scan kernel's algorithmic bytes (split bytes read +
 `cpu_baseline` = the oracle's restatement of grep.go Map (per-line
 regexp compile, as grep.go:21 does) on one host core, on a bounded prefix
 sample of the same split.
+
+A plain run does what `value` needs and no more: it generates the split,
+warms up, times --steps steps, writes the last step's records if
+--dump-outputs is given and prints the line (`config.verified`,
+`cpu_baseline*` and `gather*` are then null or absent; `roofline` comes from
+the timed steps' own HIP events). --full adds the parity check against the
+oracle, the check of the gathered records and the CPU baselines.
 """
 import argparse
 import json
@@ -114,12 +121,19 @@ def parse():
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: c2 on one GPU, c5 on more")
     ap.add_argument("--split-gib", type=float, default=None, help="per-GPU split size (default: workload's)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the parity check "
+                         "against the oracle (--verify), the check of the gathered records and the CPU baselines. "
+                         "Without it the run sets up, warms up, times the steps and prints the line (those fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's records (what dgrep_scan_device handed its "
+                         "caller) as DIR/<name>.npy in float64, see dump_outputs")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="CPU baseline budget: whole 1 MiB pieces of the split until this much time is spent")
+                    help="with --full: CPU baseline budget, whole 1 MiB pieces of the split until this much time is spent")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--verify", choices=["full", "windows", "none"], default="full",
-                    help="after the timed steps: every record of the split against the oracle over the whole split "
-                         "(full; each rank its own split), or --verify-windows whole-line windows")
+                    help="with --full, after the timed steps: every record of the split against the oracle over the "
+                         "whole split (full; each rank its own split), or --verify-windows whole-line windows")
     ap.add_argument("--verify-seconds", type=float, default=240.0,
                     help="full verification stops (and says how far it got) after this much wall time")
     ap.add_argument("--verify-windows", type=int, default=6)
@@ -183,6 +197,9 @@ def main():
     if args.gpus is not None and args.gpus < 1:
         log("bench.py --gpus must be >= 1")
         sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        log("bench.py --steps must be >= 1 and --warmup >= 0")
+        sys.exit(2)
 
     import torch
     import torch.distributed as dist
@@ -211,11 +228,17 @@ def main():
 
     m = (measure_dry if args.dry_run else measure_gpu)(args, wl, world, rank, local, dev, n, pattern, seed)
     count = m["count"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["line"], m["start"], m["len"], count, world, rank)
+    if not args.full:
+        log("plain run: no parity check, gather check or CPU baselines (--full runs them)")
 
-    # ---- parity on the full split: every rank checks its own ----------------
+    # ---- parity on the full split: every rank checks its own (--full) -------
     verified = None
     if args.dry_run:
         verified = {"mode": "none (dry run: the records are the oracle's own)"}
+    elif not args.full:
+        pass
     elif args.verify == "full":
         threads = verify_threads(world)
         verified = verify_full(m["buf"], n, m["line"][:count], m["start"][:count], m["len"][:count], pattern,
@@ -231,16 +254,16 @@ def main():
 
     # ---- the exchange: what rank 0 received in the last timed step ----------
     gather = None
-    if world > 1 or m["comm"] is not None:
+    if args.full and (world > 1 or m["comm"] is not None):
         gather = check_gather(m, world, rank, dev, seed)
-        if m["comm"] is not None:
-            m["comm"].close()
+    if m["comm"] is not None:
+        m["comm"].close()
 
-    # ---- CPU comparators, on rank 0 while the other ranks wait ---------------
+    # ---- CPU comparators (--full), on rank 0 while the other ranks wait ------
     cpu = cpu_mt = cpu_workers = None
     if world > 1:
         dist.barrier()
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         if world == 1:
             cpu = cpu_baseline(m["buf"], n, pattern, args.cpu_seconds)
             cpu_mt = cpu_baseline_mt(m["buf"], n, pattern, args.cpu_seconds / 2)
@@ -531,6 +554,7 @@ def build_line(args, wl, world, rank, dev, n, pattern, seed, m, verified, cpu, c
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(ms_step, 4),
+        "full": bool(args.full),
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -592,10 +616,46 @@ def build_line(args, wl, world, rank, dev, n, pattern, seed, m, verified, cpu, c
         out["exchange"] = gather["exchange"] if gather else m["exchange"]
         out["gather_verified"] = bool(gather and gather["gather_verified"])
         out["gather"] = gather
+    elif world > 1:  # a plain run: the gather was timed, its check is --full's
+        out["exchange"] = m["exchange"]
     if args.dry_run:
         out["dry_run"] = ("CPU rehearsal (gloo): the split is scanned by the oracle, not by the GPU; "
                           "value is null and no number here measures this framework")
     return out
+
+
+DUMP_SAMPLE = 1_500_000  # records per dumped array: 4 float64 arrays of this many stay under 64 MB
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, line_t, start_t, len_t, count, world, rank):
+    """--dump-outputs DIR: what the last timed step handed its caller -- the
+    `count` matching lines' (line number, start, length) records -- as
+    DIR/line.npy, start.npy and len.npy (float64: every value is below 2**53,
+    so exact). Past DUMP_SAMPLE records the three hold the records at the
+    ascending indices of index.npy, a sample drawn with a fixed seed (the same
+    indices for the same count). totals.npy covers every record: the count and
+    the sums of the three arrays modulo 2**52. The split and the pattern are
+    seeded, so two builds run with the same arguments dump comparable files.
+    At N > 1 each rank writes its own records as <name>_rank<r>.npy."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    if count > DUMP_SAMPLE:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, count, DUMP_SAMPLE))
+    else:
+        idx = np.arange(count, dtype=np.int64)
+    sel = torch.from_numpy(idx).to(line_t.device)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    totals = [float(count)]
+    for name, t in (("line", line_t), ("start", start_t), ("len", len_t)):
+        t = t[:count].to(torch.int64)
+        totals.append(float(int(t.sum()) % (1 << 52)))
+        np.save(os.path.join(path, name + suffix + ".npy"), t[sel].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "index" + suffix + ".npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "totals" + suffix + ".npy"), np.array(totals, dtype=np.float64))
+    log("rank %d: wrote %d of %d records to %s" % (rank, len(idx), count, path))
 
 
 def last_newline(host):

@@ -13,8 +13,8 @@ reference's application/grep.go:
 For every documented command the files the build would take must declare
 disjoint top-level names and export Map / Reduce with the reference's
 signatures (application/grep.go:13,38; looked up by main/worker_launch.go:21-34).
-CPU only; the reference's grep.go is read when present (this container), and
-its declarations are pinned below for machines without it.
+CPU only; the reference's grep.go is not part of this repository: its
+declarations are pinned below and a stand-in file is made from them.
 """
 import os
 import re
@@ -23,9 +23,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GPU_GO = os.path.join(ROOT, "application", "grep_gpu.go")
-REF_GO = "/root/reference/application/grep.go"
-# The reference's application/grep.go as declarations (grep.go:11,13,38),
-# used when the reference tree is absent.
+# The reference's application/grep.go as declarations (grep.go:11,13,38)
 REF_DECLS = {
     "pattern": "var",
     "Map": "func(filename string, contents string) []mapreduce.KeyValue",
@@ -173,12 +171,9 @@ def top_level_decls(src):
 
 
 def reference_source(patched):
-    if os.path.exists(REF_GO):
-        src = open(REF_GO).read()
-    else:
-        src = "package main\n\n" + "".join(
-            ("var %s string = \"\"\n" % k) if v == "var" else "func %s%s { }\n" % (k, v[4:])
-            for k, v in REF_DECLS.items())
+    src = "package main\n\n" + "".join(
+        ("var %s string = \"\"\n" % k) if v == "var" else "func %s%s { }\n" % (k, v[4:])
+        for k, v in REF_DECLS.items())
     return (REF_PATCH + "\n\n" + src) if patched else src
 
 
@@ -225,13 +220,6 @@ def test_decl_parser_sees_both_files():
     assert all(len(v) == 1 for v in gpu.values()), gpu
     # a file that redeclares is caught
     assert collisions({"a.go": "package main\nfunc Map() {}\n", "b.go": "package main\nvar (\n\tx int\n\tMap int\n)\n"})
-
-
-@pytest.mark.skipif(not os.path.exists(REF_GO), reason="reference tree absent")
-def test_pinned_reference_declarations():
-    ref = top_level_decls(open(REF_GO).read())
-    assert {k: v[0] for k, v in ref.items()} == {"pattern": "var", "Map": REF_DECLS["Map"],
-                                                 "Reduce": REF_DECLS["Reduce"]}
 
 
 def test_plugin_file_has_constraint_and_no_paths():

@@ -10,6 +10,6 @@ REPS=1 timeout -k 10 300 bash "$R/tools/variant_bench.sh" long_c4 base f32 > "$O
 cd "$R"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q -rs --timeout 300 --timeout-method thread > "$OUT/pytest_gpu.log" 2>&1 || exit 1
 for w in c4 long_c4p; do
-  timeout -k 10 300 python3 bench.py --workload $w > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" || exit 1
+  timeout -k 10 300 python3 bench.py --full --workload $w > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" || exit 1
 done
 echo "f64 check done"

@@ -10,7 +10,7 @@ mkdir -p "$O"
 cd "$R"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q -rs --timeout 300 --timeout-method thread > "$O/pytest_gpu.log" 2>&1
 for w in $WLS; do
-  timeout -k 10 240 python bench.py --workload "$w" > "$O/bench_$w.json" 2> "$O/bench_$w.err"
+  timeout -k 10 240 python bench.py --full --workload "$w" > "$O/bench_$w.json" 2> "$O/bench_$w.err"
 done
 for w in $PWLS; do
   timeout -k 10 400 bash tools/profile_gpu.sh "${TAG}_$w" --workload "$w"

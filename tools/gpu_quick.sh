@@ -14,6 +14,6 @@ if [ "$K" != "-" ]; then
     > "$OUT/pytest_gpu.log" 2>&1
 fi
 for w in "$@"; do
-  timeout -k 10 300 python bench.py --workload "$w" --no-cpu-baseline > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
+  timeout -k 10 300 python bench.py --full --workload "$w" --no-cpu-baseline > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
 done
 echo "quick done: $OUT"

@@ -15,6 +15,6 @@ if [ -n "$FIRST" ]; then
 fi
 timeout -k 10 1200 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > "$OUT/pytest_gpu.log" 2>&1
 for w in $WLS; do
-  timeout -k 10 400 python bench.py --workload "$w" > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
+  timeout -k 10 400 python bench.py --full --workload "$w" > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
 done
 echo "round script done: $OUT"

@@ -8,5 +8,5 @@ mkdir -p "$OUT"
 REPS=2 timeout -k 10 400 bash "$R/tools/variant_bench.sh" c3 base p8 base p8 > "$OUT/ab_c3.txt" 2>&1 || exit 1
 cd "$R"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q -rs --timeout 300 --timeout-method thread > "$OUT/pytest_gpu.log" 2>&1 || exit 1
-timeout -k 10 300 python3 bench.py --workload c3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" || exit 1
+timeout -k 10 300 python3 bench.py --full --workload c3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" || exit 1
 echo "p7 check done"

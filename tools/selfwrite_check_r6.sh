@@ -8,5 +8,5 @@ mkdir -p "$OUT"
 cd "$R"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q -rs --timeout 300 --timeout-method thread > "$OUT/pytest_gpu.log" 2>&1 || exit 1
 REPS=2 timeout -k 10 300 bash "$R/tools/variant_bench.sh" c4 base old base old > "$OUT/ab_c4.txt" 2>&1 || exit 1
-timeout -k 10 300 python3 bench.py --workload c4 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err" || exit 1
+timeout -k 10 300 python3 bench.py --full --workload c4 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err" || exit 1
 echo "selfwrite done"

@@ -11,6 +11,6 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q -rs --timeout 300 --tim
 REPS=2 timeout -k 10 300 bash "$R/tools/variant_bench.sh" c4 base old base old > "$OUT/ab_c4.txt" 2>&1 || exit 1
 REPS=1 timeout -k 10 300 bash "$R/tools/variant_bench.sh" long_c4p base old base old > "$OUT/ab_long_c4p.txt" 2>&1 || exit 1
 for w in c4 long_c4p; do
-  timeout -k 10 300 python3 bench.py --workload $w > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" || exit 1
+  timeout -k 10 300 python3 bench.py --full --workload $w > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" || exit 1
 done
 echo "verify2 done"
