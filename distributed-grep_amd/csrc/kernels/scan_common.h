@@ -181,6 +181,10 @@ struct LongDfaArgs {
   // rows), then a DfaXRec per state >= x_hot at byte xr_off
   const uint8_t* ximg;
   uint32_t ximg_bytes, x_hot, xr_off;
+  // [2] long_dfa_fix_kernel's tallies (dgrep_scan_stats long_segments,
+  // long_guess_misses): segments entered in a non-absorbing state, and those
+  // of them no guess fitted (re-run from the true state); one add per line
+  unsigned long long* walk_count;
 };
 // DfaXRec: a state past the LDS image's first rows reads the row of a resident
 // DEFAULT state except in at most two classes (keyword automata: 4,608 of

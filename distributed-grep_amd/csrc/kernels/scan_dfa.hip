@@ -2520,7 +2520,9 @@ __global__ __launch_bounds__(256) void long_dfa_fix_kernel(LongDfaArgs la) {
       }
     };
     if (g0 < ge) load(g0, gv, xv);
+    uint32_t walked = 0, missed = 0;  // this line's segments entered / re-run (la.walk_count)
     for (uint64_t g = g0; g < ge && s != la.matched && s != la.dead; ++g) {
+      ++walked;
       uint32_t gn[kLongGuesses], xn[kLongGuesses];
       load(min(g + 1, ge - 1), gn, xn);
       uint32_t x = kNoGuess;
@@ -2534,10 +2536,13 @@ __global__ __launch_bounds__(256) void long_dfa_fix_kernel(LongDfaArgs la) {
       if (x != kNoGuess) {
         s = x;
       } else {
+        ++missed;
         const LongSeg sg = la.seg[g];
         s = d.run(la.data, sg.begin, sg.end, s, la.matched);
       }
     }
+    atomicAdd(la.walk_count, (unsigned long long)walked);
+    atomicAdd(la.walk_count + 1, (unsigned long long)missed);
     P.matched = (s == la.matched || d.next(s, uint32_t('\n')) == la.start_m) ? 1u : 0u;
     P.len = P.end - P.line_start;
     la.pend[i] = P;

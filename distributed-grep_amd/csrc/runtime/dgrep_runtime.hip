@@ -82,6 +82,7 @@ uint32_t verify_hot_bytes();
 using namespace dgrep;
 
 constexpr size_t kCounters = 8;
+constexpr size_t kCtrLongWalk = 5;  // [5], [6]: long_dfa_fix_kernel's segments walked / re-run
 
 // StepPair image offsets and thresholds (see StepPair in scan_dfa.hip)
 struct PairArgs {
@@ -942,9 +943,15 @@ static int resolve_long_filter(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, 
   la.ximg_bytes = c->ximg_bytes;
   la.x_hot = c->x_hot;
   la.xr_off = c->xr_off;
+  // the fix kernel's tallies: two of the scan's counters, zeroed before the scan
+  la.walk_count = c->d_counters + kCtrLongWalk;
   HIPCHK(long_lines_dfa(la, c->full_u32, c->stream));
+  unsigned long long walk[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(walk, la.walk_count, sizeof walk, hipMemcpyDeviceToHost, c->stream));
   // the host vectors are read by the async copies above: wait before they go
   HIPCHK(hipStreamSynchronize(c->stream));
+  c->stats.long_segments = uint32_t(std::min<unsigned long long>(walk[0], UINT32_MAX));
+  c->stats.long_guess_misses = uint32_t(std::min<unsigned long long>(walk[1], UINT32_MAX));
   return DGREP_OK;
 }
 

@@ -94,7 +94,7 @@ class _ScanStats(ctypes.Structure):
                 ("scan_attempts", ctypes.c_uint32), ("tiles", ctypes.c_uint64), ("overflow_lanes", ctypes.c_uint64),
                 ("matches", ctypes.c_uint64), ("scan_ms", ctypes.c_float), ("overflow_ms", ctypes.c_float),
                 ("verify_ms", ctypes.c_float), ("candidates", ctypes.c_uint64), ("pending", ctypes.c_uint64),
-                ("reserved0", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+                ("long_guess_misses", ctypes.c_uint32), ("long_segments", ctypes.c_uint32)]
 
 
 class _Gathered(ctypes.Structure):

@@ -286,8 +286,10 @@ typedef struct {
                               of the parked long lines */
   uint64_t candidates;     /* filter stepper: candidate lines dropped by that re-run */
   uint64_t pending;        /* Sheng: long lines parked by the scan and resolved from chunk maps */
-  uint32_t reserved0;      /* round 5's order_in_scan (the in-scan ordering was removed in round 6): 0 */
-  uint32_t reserved;
+  uint32_t long_guess_misses; /* filter stepper (> 256 states): segments of parked lines whose true entry state
+                                 was none of the guessed ones, re-run serially from it (saturates) */
+  uint32_t long_segments;     /* filter stepper: segments of parked lines entered in a non-absorbing state
+                                 (saturates); both 0 when no filter line was parked */
 } dgrep_scan_stats;
 /* Sized getter: out_size is the caller's sizeof(dgrep_scan_stats). The library
  * writes min(out_size, its own size) bytes, so a binding built against an
