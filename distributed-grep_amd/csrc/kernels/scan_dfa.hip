@@ -32,7 +32,8 @@
 //         vector V[b][s] = next state; a step is ONE v_perm_b32 selecting byte
 //         s of V[b] (SDWA does the byte extract for the ds_read_b64 address).
 //         The dependent chain is a single VALU op per byte; the LDS reads do
-//         not depend on the state, so their latency overlaps.
+//         not depend on the state, so their latency overlaps: they are issued
+//         a word ahead and the chain waits for them once per word (apply).
 //       StepTable (DFA <= 256 states): u8 table [state][byte] with 260-byte
 //         rows (bank-staggered); a step is v_perm (row|byte) + v_lshl_add +
 //         ds_read_u8 on the dependent chain.
@@ -200,6 +201,19 @@ struct StepSheng8 {
   }
   __device__ __forceinline__ void apply(const Pre& p, uint32_t s, uint32_t& s0, uint32_t& s1, uint32_t& s2,
                                         uint32_t& s3) const {
+    // ONE LDS wait per word. run_block issues the next word's four V reads
+    // before this point and LDS reads return in order: once at most four
+    // reads are outstanding, all four of THIS word have landed. Without the
+    // explicit s_waitcnt lgkmcnt(4) (vmcnt 63 and expcnt 7: no wait) the
+    // compiler puts lgkmcnt(7/6/5/4) in front of the four v_perm, three more
+    // instructions in the wave's in-order stream per word. Its own wait
+    // insertion still runs after this one and adds what else is needed (the
+    // block's last word has no younger reads). The sched_barrier pins the
+    // wait in front of the chain: the scheduler otherwise sinks it below the
+    // v_perm, and the four waits come back. Same-box A/B: C2 +1.5-2.3 %
+    // (DESIGN.md §3.2, round 7).
+    __builtin_amdgcn_s_waitcnt(0xc47f);
+    __builtin_amdgcn_sched_barrier(0);
     s0 = sel(p.m0, s);
     s1 = sel(p.m1, s0);
     s2 = sel(p.m2, s1);
