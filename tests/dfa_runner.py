@@ -8,16 +8,45 @@ Used to check the pattern compiler against the oracle on the CPU.
 import numpy as np
 
 
-def run_blob(cp, data: bytes):
-    bc, tr = cp.tables()
-    nl = int(bc[10])
+class _ByteRows:
+    """row(s)[b] = next state of s on byte b, as plain lists built when a state
+    is first entered (the walk is a Python loop: list indexing is several
+    times faster than numpy's, and a large DFA's unvisited rows cost nothing)."""
+
+    def __init__(self, cp):
+        bc, tr = cp.tables()
+        self.cls = bc.tolist()
+        self.tr = tr
+        self.rows = [None] * cp.nstates
+
+    def row(self, s):
+        r = self.rows[s]
+        if r is None:
+            t = self.tr[s].tolist()
+            r = self.rows[s] = [t[c] for c in self.cls]
+        return r
+
+
+def _byte_rows(cp):
+    br = getattr(cp, "_byte_rows", None)
+    if br is None:
+        br = cp._byte_rows = _ByteRows(cp)
+    return br
+
+
+def run_blob(cp, data: bytes, visited=None):
+    """visited: a set that receives every state id the walk enters."""
+    br = _byte_rows(cp)
+    rows, row = br.rows, br.row
     s = cp.start
     M = cp.start_m
     out_ln, out_st, out_le = [], [], []
     line = 1
     ls = 0
     for i, b in enumerate(data):
-        s = int(tr[s, bc[b]])
+        s = (rows[s] or row(s))[b]
+        if visited is not None:
+            visited.add(s)
         if b == 10:
             if s == M:
                 out_ln.append(line)
@@ -25,7 +54,7 @@ def run_blob(cp, data: bytes):
                 out_le.append(i - ls)
             line += 1
             ls = i + 1
-    if int(tr[s, nl]) == M:
+    if row(s)[10] == M:
         out_ln.append(line)
         out_st.append(ls)
         out_le.append(len(data) - ls)
