@@ -20,10 +20,12 @@
 
 #include "../../../include/dgrep.h"
 #include "../../../include/dgrep_blob.h"
+#include "../kernels/batch.h"
 #include "../kernels/encode.h"
 #include "../kernels/reduce.h"
 #include "../kernels/scan_common.h"
 #include "../kernels/synth.h"
+#include "pack_pieces.h"
 
 // DFAs of at most this many states use the Sheng stepper (8 = its limit; 0
 // sends every DFA of <= 256 states to the table stepper)
@@ -208,6 +210,22 @@ struct dgrep_ctx {
   uint8_t* d_enc_out = nullptr;
   uint64_t enc_out_cap = 0;
   float last_encode_ms = 0.f;
+
+  // many splits in one scan (dgrep_scan_batch*, kernels/batch.h)
+  uint64_t* d_bat_begin = nullptr;  // [k + 1]
+  uint64_t bat_begin_cap = 0;
+  unsigned long long* d_bat_lines = nullptr;  // [k]
+  uint64_t bat_lines_cap = 0;
+  unsigned long long* d_bat_sums = nullptr;   // [kBatchScanBlocks] + the separator flag
+  unsigned long long* h_bat_flag = nullptr;   // pinned: the flag's readback rides the scan's own host wait
+  std::vector<uint64_t> bat_begin;            // host copy of begin[] (read by an async upload)
+  std::vector<uint8_t> bat_stage;             // the direct ingest path's one staging buffer
+  uint32_t* d_res_split = nullptr;            // dgrep_scan_batch (host data) results, with d_res_*
+  uint64_t res_split_cap = 0;
+  uint64_t* d_res_sbegin = nullptr;
+  uint64_t res_sbegin_cap = 0;
+  hipEvent_t evb0 = nullptr, evb1 = nullptr, evb2 = nullptr, evb3 = nullptr;
+  float last_newline_ms = 0.f, last_rebase_ms = 0.f;
 
   // reduce task (dgrep_reduce)
   uint8_t* d_red_scratch = nullptr;
@@ -534,7 +552,8 @@ extern "C" void dgrep_close(dgrep_ctx* c) {
   void* bufs[] = {c->d_table, c->d_full, c->d_ximg, c->d_nfa, c->d_cls, c->d_spill, c->d_tails, c->d_chunk_nl, c->d_chunk_map,
                   c->d_pend, c->d_long_tbl, c->d_st2id, c->d_seg, c->d_seg_off, c->d_segmap, c->d_seg_from, c->d_seg_state, c->d_tiles, c->d_out_off, c->d_line_base, c->d_staging, c->d_counters,
                   c->d_overflow, c->d_data, c->d_res_line, c->d_res_start, c->d_res_len, c->d_enc_scratch,
-                  c->d_fname, c->d_bounds, c->d_enc_out, c->d_red_scratch, c->d_red_out};
+                  c->d_fname, c->d_bounds, c->d_enc_out, c->d_red_scratch, c->d_red_out, c->d_bat_begin,
+                  c->d_bat_lines, c->d_bat_sums, c->d_res_split, c->d_res_sbegin};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
@@ -549,6 +568,9 @@ extern "C" void dgrep_close(dgrep_ctx* c) {
   if (c->ev3) (void)hipEventDestroy(c->ev3);
   if (c->ev4) (void)hipEventDestroy(c->ev4);
   if (c->ev5) (void)hipEventDestroy(c->ev5);
+  for (hipEvent_t e : {c->evb0, c->evb1, c->evb2, c->evb3})
+    if (e) (void)hipEventDestroy(e);
+  if (c->h_bat_flag) (void)hipHostFree(c->h_bat_flag);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }
@@ -1352,6 +1374,21 @@ extern "C" int dgrep_last_ingest_ms(dgrep_ctx* c, float* ms) {
   return DGREP_OK;
 }
 
+// The context's result arrays, at least `want` lines each.
+static int grow_results(dgrep_ctx* c, uint64_t want) {
+  if (want <= c->res_cap) return DGREP_OK;
+  int rc;
+  uint64_t c1 = 0, c2 = 0, c3 = 0;
+  if (c->d_res_line) { HIPCHK(hipFree(c->d_res_line)); c->d_res_line = nullptr; }
+  if (c->d_res_start) { HIPCHK(hipFree(c->d_res_start)); c->d_res_start = nullptr; }
+  if (c->d_res_len) { HIPCHK(hipFree(c->d_res_len)); c->d_res_len = nullptr; }
+  if ((rc = grow(c, &c->d_res_line, &c1, want)) != DGREP_OK) return rc;
+  if ((rc = grow(c, &c->d_res_start, &c2, want)) != DGREP_OK) return rc;
+  if ((rc = grow(c, &c->d_res_len, &c3, want)) != DGREP_OK) return rc;
+  c->res_cap = want;
+  return DGREP_OK;
+}
+
 // Host split -> HBM (ingest) -> scan into the context's result arrays.
 static int scan_host(dgrep_ctx* c, const uint8_t* data, size_t n, uint64_t* count) {
   int rc;
@@ -1363,16 +1400,7 @@ static int scan_host(dgrep_ctx* c, const uint8_t* data, size_t n, uint64_t* coun
   }
   uint64_t want = std::max<uint64_t>(c->res_cap, std::max<uint64_t>(1024, n / 512));
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if (want > c->res_cap) {
-      uint64_t c1 = 0, c2 = 0, c3 = 0;
-      if (c->d_res_line) { HIPCHK(hipFree(c->d_res_line)); c->d_res_line = nullptr; }
-      if (c->d_res_start) { HIPCHK(hipFree(c->d_res_start)); c->d_res_start = nullptr; }
-      if (c->d_res_len) { HIPCHK(hipFree(c->d_res_len)); c->d_res_len = nullptr; }
-      if ((rc = grow(c, &c->d_res_line, &c1, want)) != DGREP_OK) return rc;
-      if ((rc = grow(c, &c->d_res_start, &c2, want)) != DGREP_OK) return rc;
-      if ((rc = grow(c, &c->d_res_len, &c3, want)) != DGREP_OK) return rc;
-      c->res_cap = want;
-    }
+    if ((rc = grow_results(c, want)) != DGREP_OK) return rc;
     if ((rc = scan_resident(c, c->d_data, n, c->d_res_line, c->d_res_start, c->d_res_len, c->res_cap, count)) !=
         DGREP_OK)
       return rc;
@@ -1403,6 +1431,281 @@ extern "C" int dgrep_scan(dgrep_ctx* c, const uint8_t* data, size_t n, dgrep_res
   HIPCHK(hipMemcpyAsync(out->start, c->d_res_start, count * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(out->len, c->d_res_len, count * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
+  return DGREP_OK;
+}
+
+// ---- many splits in one scan (kernels/batch.h) ------------------------------
+// One map task per input file (map_reduce/coordinator.go:312,329-333) makes a
+// worker's files many small splits. Packed with one '\n' between them they
+// split into exactly the splits' lines, so one scan_resident over the packed
+// buffer finds every matching line; the batch kernels rebase the records.
+
+// The batch scratch for k splits, and begin[] (c->bat_begin, k + 1 entries).
+static int batch_setup(dgrep_ctx* c, const uint64_t* len, uint64_t k) {
+  int rc;
+  if ((rc = grow(c, &c->d_bat_begin, &c->bat_begin_cap, k + 1)) != DGREP_OK) return rc;
+  if ((rc = grow(c, &c->d_bat_lines, &c->bat_lines_cap, k)) != DGREP_OK) return rc;
+  if (!c->d_bat_sums)
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_bat_sums), (kBatchScanBlocks + 1) * sizeof(unsigned long long)));
+  if (!c->h_bat_flag) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_bat_flag), 8, hipHostMallocDefault));
+  for (hipEvent_t* e : {&c->evb0, &c->evb1, &c->evb2, &c->evb3})
+    if (!*e) HIPCHK(hipEventCreate(e));
+  c->bat_begin.resize(k + 1);
+  uint64_t b = 0;
+  for (uint64_t i = 0; i < k; ++i) {
+    c->bat_begin[i] = b;
+    b += len[i] + 1;
+  }
+  c->bat_begin[k] = b;  // n_packed + 1: closes the last region
+  return DGREP_OK;
+}
+
+// Core of both batch forms: P (n bytes, k splits, begin[] in c->bat_begin) is
+// resident at d_packed. `prepass`: count the lines before each split and check
+// the separators first -- once per P; a re-scan into larger arrays reuses them.
+// The kernels are queued on the context stream around scan_resident's own
+// work; the separator flag's readback is queued before the scan, so the scan's
+// host wait delivers it, and the one wait added is the one after the rebase.
+static int batch_resident(dgrep_ctx* c, const uint8_t* d_packed, uint64_t n, uint64_t k, uint64_t* d_line,
+                          uint64_t* d_start, uint64_t* d_len, uint32_t* d_split, uint64_t* d_split_begin,
+                          uint64_t capacity, uint64_t* count, bool prepass) {
+  *count = 0;
+  BatchArgs b;
+  b.data = d_packed;
+  b.n = n;
+  b.begin = c->d_bat_begin;
+  b.k = k;
+  b.lines = c->d_bat_lines;
+  b.block_sums = c->d_bat_sums;
+  b.bad_split = c->d_bat_sums + kBatchScanBlocks;
+  if (prepass) {
+    if (n && (reinterpret_cast<uintptr_t>(d_packed) & 15)) {
+      c->err = "device split must be 16-byte aligned";
+      return DGREP_E_INVALID;
+    }
+    c->last_newline_ms = c->last_rebase_ms = 0.f;
+    *c->h_bat_flag = UINT64_MAX;
+    HIPCHK(hipMemcpyAsync(c->d_bat_begin, c->bat_begin.data(), (k + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_bat_lines, 0, k * 8, c->stream));
+    HIPCHK(hipMemsetAsync(b.bad_split, 0xff, 8, c->stream));
+    HIPCHK(hipEventRecord(c->evb0, c->stream));
+    HIPCHK(batch_split_newlines(b, c->num_cus, c->stream));
+    HIPCHK(hipEventRecord(c->evb1, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_bat_flag, b.bad_split, 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  int rc;
+  if ((rc = scan_resident(c, d_packed, n, d_line, d_start, d_len, capacity, count)) != DGREP_OK) return rc;
+  if (prepass) {
+    // scan_resident waited for the stream unless it had nothing to scan
+    if (n == 0 || (c->flags & DGREP_DFA_MATCH_NONE)) HIPCHK(hipStreamSynchronize(c->stream));
+    if (*c->h_bat_flag != UINT64_MAX) {
+      c->err = "packed buffer: the byte after split " + std::to_string(*c->h_bat_flag) + " is not '\\n'";
+      *count = 0;
+      return DGREP_E_INVALID;
+    }
+    HIPCHK(hipEventElapsedTime(&c->last_newline_ms, c->evb0, c->evb1));
+  }
+  const uint64_t nrec = std::min(*count, capacity);
+  HIPCHK(hipEventRecord(c->evb2, c->stream));
+  // the ranges are searched in the scan's packed-buffer starts: before the rebase
+  if (d_split_begin && *count <= capacity)
+    HIPCHK(batch_split_ranges(b, d_start, nrec, d_split_begin, c->num_cus, c->stream));
+  HIPCHK(batch_rebase(b, d_line, d_start, d_split, nrec, c->num_cus, c->stream));
+  HIPCHK(hipEventRecord(c->evb3, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->last_rebase_ms, c->evb2, c->evb3));
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_scan_batch_device(dgrep_ctx* c, const void* d_packed, size_t n_packed, const uint64_t* split_len,
+                                       size_t nsplits, uint64_t* d_line_no, uint64_t* d_start, uint64_t* d_len,
+                                       uint32_t* d_split, uint64_t* d_split_begin, uint64_t capacity,
+                                       uint64_t* count) {
+  if (count) *count = 0;
+  if (!c || !count || !split_len || nsplits == 0 || nsplits > UINT32_MAX || (n_packed && !d_packed) ||
+      (capacity && (!d_line_no || !d_start || !d_len || !d_split)))
+    return DGREP_E_INVALID;
+  uint64_t total = nsplits - 1;
+  for (size_t i = 0; i < nsplits; ++i) {
+    if (split_len[i] > UINT64_MAX - 1 - total) {
+      c->err = "dgrep_scan_batch_device: the split lengths overflow";
+      return DGREP_E_INVALID;
+    }
+    total += split_len[i];
+  }
+  if (total != n_packed) {
+    c->err = "dgrep_scan_batch_device: n_packed must be the split lengths plus nsplits - 1 separators";
+    return DGREP_E_INVALID;
+  }
+  if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  if ((rc = batch_setup(c, split_len, nsplits)) != DGREP_OK) return rc;
+  rc = batch_resident(c, static_cast<const uint8_t*>(d_packed), n_packed, nsplits, d_line_no, d_start, d_len, d_split,
+                      d_split_begin, capacity, count, true);
+  if (rc == DGREP_OK) {
+    c->ms_sum += c->last_ms;
+    ++c->ms_scans;
+  }
+  return rc;
+}
+
+// The pinned staging ring of the ingest, as ingest() sets it up.
+static int ingest_ring(dgrep_ctx* c, size_t S, int B) {
+  if (c->stage_bytes != S || int(c->h_stage.size()) != B) {
+    if (c->copy_stream) HIPCHK(hipStreamSynchronize(c->copy_stream));
+    for (uint8_t* h : c->h_stage)
+      if (h) HIPCHK(hipHostFree(h));
+    for (hipEvent_t e : c->ev_stage)
+      if (e) HIPCHK(hipEventDestroy(e));
+    c->h_stage.assign(B, nullptr);
+    c->ev_stage.assign(B, nullptr);
+    c->stage_bytes = 0;
+    for (int b = 0; b < B; ++b) {
+      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage[b]), S, hipHostMallocDefault));
+      HIPCHK(hipEventCreateWithFlags(&c->ev_stage[b], hipEventDisableTiming));
+    }
+    c->stage_bytes = S;
+  }
+  if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  return DGREP_OK;
+}
+
+// ingest() for a batch: the packed buffer is never built on the host. Each
+// pinned staging piece is filled from the runs of source splits and separator
+// bytes that fall into it (pack_pieces.h), then DMA'd as in ingest(): the same
+// ring, copy stream and settings. Below 4 MiB, or with chunk 0, the whole of P
+// is assembled in one host staging buffer and copied with one hipMemcpyAsync.
+static int ingest_packed(dgrep_ctx* c, const uint8_t* const* data, const size_t* n, size_t k, size_t total) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int T = std::max(1, c->ingest_threads);
+  PackCursor cur;
+  std::vector<PackSeg> segs;
+  auto fill = [&](uint8_t* dst, size_t len) {
+    pack_piece_segments(n, k, &cur, len, &segs);
+    for (const PackSeg& s : segs) {
+      if (T == 1 || s.split == kPackSeparator || s.len < (size_t(1) << 20)) {
+        pack_copy_segment(data, s, dst);
+        continue;
+      }
+      std::vector<std::thread> th;
+      const size_t part = ((s.len + T - 1) / T + 4095) & ~size_t(4095);
+      uint8_t* d = dst + s.dst_off;
+      const uint8_t* src = data[s.split] + s.src_off;
+      const size_t len_s = s.len;
+      for (int t = 0; t < T; ++t) {
+        const size_t a = size_t(t) * part;
+        if (a >= len_s) break;
+        const size_t m = std::min(part, len_s - a);
+        th.emplace_back([=] { memcpy(d + a, src + a, m); });
+      }
+      for (auto& x : th) x.join();
+    }
+  };
+  if (c->ingest_chunk == 0 || total < (size_t(4) << 20)) {
+    c->bat_stage.resize(total);
+    fill(c->bat_stage.data(), total);
+    HIPCHK(hipMemcpyAsync(c->d_data, c->bat_stage.data(), total, hipMemcpyHostToDevice, c->stream));
+    c->last_ingest_ms = 0.f;
+    return DGREP_OK;
+  }
+  const size_t S = c->ingest_chunk;
+  const int B = std::max(2, c->ingest_bufs);
+  int rc;
+  if ((rc = ingest_ring(c, S, B)) != DGREP_OK) return rc;
+  // the previous scan may still read d_data: the first DMA waits for it
+  HIPCHK(hipEventRecord(c->ev1, c->stream));
+  HIPCHK(hipStreamWaitEvent(c->copy_stream, c->ev1, 0));
+  std::vector<bool> used(B, false);
+  const size_t pieces = (total + S - 1) / S;
+  for (size_t p = 0; p < pieces; ++p) {
+    const int b = int(p % size_t(B));
+    const size_t off = p * S, len = std::min(S, total - off);
+    if (used[b]) HIPCHK(hipEventSynchronize(c->ev_stage[b]));  // buffer b's last DMA is done
+    fill(c->h_stage[b], len);
+    HIPCHK(hipMemcpyAsync(c->d_data + off, c->h_stage[b], len, hipMemcpyHostToDevice, c->copy_stream));
+    HIPCHK(hipEventRecord(c->ev_stage[b], c->copy_stream));
+    used[b] = true;
+  }
+  HIPCHK(hipStreamWaitEvent(c->stream, c->ev_stage[int((pieces - 1) % size_t(B))], 0));
+  HIPCHK(hipStreamSynchronize(c->copy_stream));
+  c->last_ingest_ms =
+      std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_scan_batch(dgrep_ctx* c, const uint8_t* const* data, const size_t* n, size_t nsplits,
+                                dgrep_batch_result* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!c || !out || !data || !n || nsplits == 0 || nsplits > UINT32_MAX) return DGREP_E_INVALID;
+  for (size_t i = 0; i < nsplits; ++i)
+    if (n[i] && !data[i]) return DGREP_E_INVALID;
+  size_t total = 0;
+  if (!pack_total(n, nsplits, &total) || total == ~size_t(0)) {
+    c->err = "dgrep_scan_batch: the split lengths overflow";
+    return DGREP_E_INVALID;
+  }
+  if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  static_assert(sizeof(size_t) == sizeof(uint64_t), "split lengths are passed on as u64");
+  if ((rc = batch_setup(c, reinterpret_cast<const uint64_t*>(n), nsplits)) != DGREP_OK) return rc;
+  if (total) {
+    uint64_t cap = c->data_cap;
+    if ((rc = grow(c, &c->d_data, &cap, (uint64_t(total) + 63) & ~uint64_t(63))) != DGREP_OK) return rc;
+    c->data_cap = cap;
+    if ((rc = ingest_packed(c, data, n, nsplits, total)) != DGREP_OK) return rc;
+  }
+  if ((rc = grow(c, &c->d_res_sbegin, &c->res_sbegin_cap, uint64_t(nsplits) + 1)) != DGREP_OK) return rc;
+  uint64_t want = std::max<uint64_t>(c->res_cap, std::max<uint64_t>(1024, total / 512));
+  uint64_t count = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if ((rc = grow_results(c, want)) != DGREP_OK) return rc;
+    if ((rc = grow(c, &c->d_res_split, &c->res_split_cap, c->res_cap)) != DGREP_OK) return rc;
+    if ((rc = batch_resident(c, c->d_data, total, nsplits, c->d_res_line, c->d_res_start, c->d_res_len, c->d_res_split,
+                             c->d_res_sbegin, c->res_cap, &count, attempt == 0)) != DGREP_OK)
+      return rc;
+    if (count <= c->res_cap) break;
+    want = count;
+  }
+  out->count = count;
+  out->nsplits = nsplits;
+  out->split_begin = static_cast<uint64_t*>(malloc((nsplits + 1) * 8));
+  if (count) {
+    out->line_no = static_cast<uint64_t*>(malloc(count * 8));
+    out->start = static_cast<uint64_t*>(malloc(count * 8));
+    out->len = static_cast<uint64_t*>(malloc(count * 8));
+    out->split = static_cast<uint32_t*>(malloc(count * 4));
+  }
+  if (!out->split_begin || (count && (!out->line_no || !out->start || !out->len || !out->split))) {
+    dgrep_batch_result_free(out);
+    return DGREP_E_NOMEM;
+  }
+  HIPCHK(hipMemcpyAsync(out->split_begin, c->d_res_sbegin, (nsplits + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  if (count) {
+    HIPCHK(hipMemcpyAsync(out->line_no, c->d_res_line, count * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out->start, c->d_res_start, count * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out->len, c->d_res_len, count * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out->split, c->d_res_split, count * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return DGREP_OK;
+}
+
+extern "C" void dgrep_batch_result_free(dgrep_batch_result* r) {
+  if (!r) return;
+  free(r->line_no);
+  free(r->start);
+  free(r->len);
+  free(r->split);
+  free(r->split_begin);
+  memset(r, 0, sizeof *r);
+}
+
+extern "C" int dgrep_last_batch_ms(dgrep_ctx* c, float* newline_ms, float* rebase_ms) {
+  if (!c || !newline_ms || !rebase_ms) return DGREP_E_INVALID;
+  *newline_ms = c->last_newline_ms;
+  *rebase_ms = c->last_rebase_ms;
   return DGREP_OK;
 }
 

@@ -57,6 +57,7 @@ EXPORTS = (
     "dgrep_reduce", "dgrep_reduce_free", "dgrep_last_scan_stats", "dgrep_build_info",
     "dgrep_comm_unique_id", "dgrep_comm_open", "dgrep_comm_close", "dgrep_gather_records_device",
     "dgrep_gather_records", "dgrep_gathered_free", "dgrep_comm_last_error",
+    "dgrep_scan_batch", "dgrep_batch_result_free", "dgrep_scan_batch_device", "dgrep_last_batch_ms",
 )
 COMM_ID_BYTES = 128
 
@@ -101,6 +102,13 @@ class _Gathered(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint64), ("line_no", ctypes.POINTER(ctypes.c_uint64)),
                 ("start", ctypes.POINTER(ctypes.c_uint64)), ("len", ctypes.POINTER(ctypes.c_uint64)),
                 ("split", ctypes.POINTER(ctypes.c_uint32))]
+
+
+class _BatchResult(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_uint64), ("line_no", ctypes.POINTER(ctypes.c_uint64)),
+                ("start", ctypes.POINTER(ctypes.c_uint64)), ("len", ctypes.POINTER(ctypes.c_uint64)),
+                ("split", ctypes.POINTER(ctypes.c_uint32)), ("nsplits", ctypes.c_uint64),
+                ("split_begin", ctypes.POINTER(ctypes.c_uint64))]
 
 
 class _BlobInfo(ctypes.Structure):
@@ -199,6 +207,14 @@ def lib() -> ctypes.CDLL:
             L.dgrep_gathered_free.restype = None
             L.dgrep_comm_last_error.argtypes = [vp]
             L.dgrep_comm_last_error.restype = ctypes.c_char_p
+            L.dgrep_scan_batch.argtypes = [vp, vp, vp, sz, ctypes.POINTER(_BatchResult)]
+            L.dgrep_scan_batch.restype = i
+            L.dgrep_batch_result_free.argtypes = [ctypes.POINTER(_BatchResult)]
+            L.dgrep_batch_result_free.restype = None
+            L.dgrep_scan_batch_device.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, u64, ctypes.POINTER(u64)]
+            L.dgrep_scan_batch_device.restype = i
+            L.dgrep_last_batch_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+            L.dgrep_last_batch_ms.restype = i
             _lib = L
     return _lib
 
@@ -343,6 +359,50 @@ class Context:
                                               ctypes.c_void_p(d_start), ctypes.c_void_p(d_len), capacity,
                                               ctypes.byref(cnt)))
         return int(cnt.value)
+
+    def scan_batch(self, splits) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Many host splits in one scan (dgrep_scan_batch): (line_no u64[], start
+        u64[], len u64[], split u32[], split_begin u64[len(splits) + 1]); line_no
+        and start are relative to the record's split, and split s owns records
+        [split_begin[s], split_begin[s+1])."""
+        raws = [x.encode("utf-8", "surrogateescape") if isinstance(x, str) else bytes(x) for x in splits]
+        k = len(raws)
+        bufs = [np.frombuffer(r, dtype=np.uint8) for r in raws]  # keep the bytes alive over the call
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[b.ctypes.data if len(b) else None for b in bufs])
+        lens = (ctypes.c_size_t * max(k, 1))(*[len(r) for r in raws])
+        res = _BatchResult()
+        self._check(self._L.dgrep_scan_batch(self._h, ptrs, lens, k, ctypes.byref(res)))
+        try:
+            n = int(res.count)
+            sb = np.ctypeslib.as_array(res.split_begin, shape=(k + 1,)).copy()
+            if n == 0:
+                return (np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint64),
+                        np.zeros(0, np.uint32), sb)
+            return (np.ctypeslib.as_array(res.line_no, shape=(n,)).copy(),
+                    np.ctypeslib.as_array(res.start, shape=(n,)).copy(),
+                    np.ctypeslib.as_array(res.len, shape=(n,)).copy(),
+                    np.ctypeslib.as_array(res.split, shape=(n,)).copy(), sb)
+        finally:
+            self._L.dgrep_batch_result_free(ctypes.byref(res))
+
+    def scan_batch_device(self, d_packed: int, n_packed: int, split_len, d_line: int, d_start: int, d_len: int,
+                          d_split: int, d_split_begin: int, capacity: int) -> int:
+        """HBM-resident packed splits (dgrep_scan_batch_device): split_len = the
+        splits' byte lengths (host), d_split_begin may be 0 (NULL); returns the
+        match count over all splits."""
+        lens = np.ascontiguousarray(split_len, dtype=np.uint64)
+        cnt = ctypes.c_uint64()
+        self._check(self._L.dgrep_scan_batch_device(
+            self._h, ctypes.c_void_p(d_packed), n_packed, ctypes.c_void_p(lens.ctypes.data if len(lens) else None),
+            len(lens), ctypes.c_void_p(d_line), ctypes.c_void_p(d_start), ctypes.c_void_p(d_len),
+            ctypes.c_void_p(d_split), ctypes.c_void_p(d_split_begin or None), capacity, ctypes.byref(cnt)))
+        return int(cnt.value)
+
+    def last_batch_ms(self) -> Tuple[float, float]:
+        """(newline_ms, rebase_ms) of the last batch call's own kernels (dgrep_last_batch_ms)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        self._check(self._L.dgrep_last_batch_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return float(a.value), float(b.value)
 
     def synth(self, d_out: int, n: int, seed: int, kind: int = 0):
         self._check(self._L.dgrep_synth_corpus(self._h, ctypes.c_void_p(d_out), n, seed, kind))
@@ -579,6 +639,28 @@ def Map(filename: str, contents) -> List[KeyValue]:
         kva.append(KeyValue(format_key(filename, n), v.decode("utf-8", "surrogateescape")
                             if isinstance(contents, str) else v))
     return kva
+
+
+def MapBatch(files: Sequence[Tuple[str, object]]) -> List[List[KeyValue]]:
+    """[Map(f, c) for f, c in files] in one scan (dgrep_scan_batch): a worker
+    that has read several input files (one map task each,
+    map_reduce/coordinator.go:312,329-333) hands them over together. No file:
+    [] without touching the GPU."""
+    files = list(files)
+    if not files:
+        return []
+    raws = [c.encode("utf-8", "surrogateescape") if isinstance(c, str) else bytes(c) for _, c in files]
+    ln, st, le, _, sb = _context().scan_batch(raws)
+    ln, st, le, sb = ln.tolist(), st.tolist(), le.tolist(), sb.tolist()
+    out = []
+    for i, (filename, contents) in enumerate(files):
+        raw, text = raws[i], isinstance(contents, str)
+        kva = []
+        for r in range(sb[i], sb[i + 1]):
+            v = raw[st[r]:st[r] + le[r]]
+            kva.append(KeyValue(format_key(filename, ln[r]), v.decode("utf-8", "surrogateescape") if text else v))
+        out.append(kva)
+    return out
 
 
 def Reduce(key: str, values: Sequence[str]) -> str:

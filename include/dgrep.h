@@ -207,6 +207,65 @@ void dgrep_reduce_free(dgrep_reduce_out* r);
 int dgrep_scan_device(dgrep_ctx* ctx, const void* d_data, size_t n, uint64_t* d_line_no, uint64_t* d_start,
                       uint64_t* d_len, uint64_t capacity, uint64_t* count);
 
+/* ---- many splits in one scan ------------------------------------------------
+ * The reference job is one map task per input file (map_reduce/coordinator.go:
+ * 312,329-333), so a worker usually holds many small splits, and a split far
+ * below the GPU's capacity leaves most of it idle. The batch form scans k
+ * splits in one launch: they are packed as P = s_0 '\n' s_1 '\n' ... '\n'
+ * s_{k-1} (one '\n' between consecutive splits, none after the last), whose
+ * strings.Split(P, "\n") is exactly the concatenation of the splits' own line
+ * lists (an empty split is one empty line; a split ending in '\n' keeps its
+ * empty last line), and each line is matched as its own string as before. One
+ * scan of P therefore finds every split's matching lines in order; the GPU then
+ * rebases line numbers and starts per split.
+ *
+ * Records are in split order, then line order; split s owns records
+ * [split_begin[s], split_begin[s+1]) (empty for a split with no match). */
+typedef struct {
+  uint64_t count;        /* matching lines over all splits */
+  uint64_t* line_no;     /* 1-based within its split */
+  uint64_t* start;       /* byte offset within its split */
+  uint64_t* len;
+  uint32_t* split;       /* index into the caller's arrays */
+  uint64_t nsplits;
+  uint64_t* split_begin; /* nsplits+1: split s owns records [split_begin[s], split_begin[s+1]) */
+} dgrep_batch_result;
+
+/* Host splits data[i][0 : n[i]) -> packed while ingested (the same staging
+ * ring and dgrep_set_ingest settings as dgrep_scan; the packed buffer is never
+ * built on the host above the 4 MiB direct path) -> one scan -> host results.
+ * DGREP_E_INVALID, with *out zeroed and before any GPU call: a null ctx, out,
+ * data or n; nsplits == 0 or > UINT32_MAX; a null data[i] with n[i] != 0; split
+ * lengths whose sum overflows. No DFA loaded: DGREP_E_NO_DFA. A
+ * DGREP_DFA_MATCH_NONE pattern gives count 0 and an all-zero split_begin.
+ * dgrep_last_scan_stats afterwards describes the scan of the packed buffer
+ * (matches = the total); dgrep_last_kernel_ms stays scan plus overflow pass. */
+int dgrep_scan_batch(dgrep_ctx* ctx, const uint8_t* const* data, const size_t* n, size_t nsplits,
+                     dgrep_batch_result* out);
+void dgrep_batch_result_free(dgrep_batch_result* r);
+
+/* Device form: the caller packed P itself (n_packed = sum of split_len +
+ * nsplits - 1 bytes at d_packed, 16-byte aligned like dgrep_scan_device's
+ * split; the other pointers need no alignment beyond their type's). Follows
+ * dgrep_scan_device's contract: `capacity` entries per result array, *count =
+ * the number of matching lines; if *count > capacity nothing is written beyond
+ * capacity, d_split_begin is not valid and the caller calls again. d_split_begin
+ * (nsplits + 1 device entries) may be NULL. DGREP_E_INVALID before any GPU
+ * call: the checks of dgrep_scan_batch, and split lengths that do not add up
+ * to n_packed. A byte other than '\n' where a separator belongs is
+ * DGREP_E_INVALID too (the message names the split) with *count = 0. Adds one
+ * host synchronisation to the scan's own. */
+int dgrep_scan_batch_device(dgrep_ctx* ctx, const void* d_packed, size_t n_packed,
+                            const uint64_t* split_len /* host, nsplits */, size_t nsplits,
+                            uint64_t* d_line_no, uint64_t* d_start, uint64_t* d_len, uint32_t* d_split,
+                            uint64_t* d_split_begin /* nsplits+1 device entries, may be NULL */,
+                            uint64_t capacity, uint64_t* count);
+
+/* Device time (ms, HIP events) of the last batch call's own kernels: counting
+ * the lines before every split (one more read of the packed buffer) and the
+ * per-split ranges + rebase of the records. */
+int dgrep_last_batch_ms(dgrep_ctx* ctx, float* newline_ms, float* rebase_ms);
+
 /* ---- multi-GPU exchange -----------------------------------
  * Replaces the SFTP shipping of map output to the reducers
  * (map_reduce/coordinator.go:136-142) for workers on one node: each worker
