@@ -11,14 +11,21 @@
 //     random order.
 // Here: the concatenated input bytes sit in HBM; a newline select gives the
 // lines; one thread per line decodes {"Key":"..","Value":".."} (JSON string
-// escapes, \uXXXX incl. surrogate pairs -> UTF-8) to measure the raw key and
-// value and hash the raw key (FNV-1a 64); a radix sort of (hash, line) groups
-// equal keys and an exact byte compare inside each equal-hash run keeps the
-// first line of every distinct key; a scan of the kept lines' output lengths
-// places "key value\n"; one thread per kept line writes it. Output order = input
-// line order of the kept lines (one of the orders the reference can produce).
-// Input must be json.Encoder KeyValue lines (what writeMapOutput writes); any
-// other line is reported as malformed (DGREP_E_INVALID), never guessed.
+// escapes, \uXXXX incl. surrogate pairs -> UTF-8, raw invalid UTF-8 -> U+FFFD
+// per byte) to measure the raw key and value and hash the raw key (FNV-1a 64);
+// a radix sort of (hash, line) groups equal keys and an exact compare of the
+// decoded keys inside each equal-hash run keeps the first line of every
+// distinct key; a scan of the kept lines' output lengths places "key value\n";
+// one wave per 64 kept lines writes them. Output order = input line order of
+// the kept lines (one of the orders the reference can produce).
+// Accepted input: lines of the compact two-field form
+//     {"Key":"<json string>","Value":"<json string>"}\n
+// byte for byte, with ANY JSON string encoding/json's decoder accepts (every
+// escape it knows, either hex case, escaped or raw runes, invalid UTF-8); on
+// such a line the key and value are exactly the decoder's. json.Encoder writes
+// this form, and only its canonical spelling of it. Everything else -- white
+// space, other field order or names, more fields, other JSON that the decoder
+// would take -- is reported as malformed (DGREP_E_INVALID), never guessed.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -35,34 +42,120 @@ __device__ inline int hexval(uint32_t c) {
   return -1;
 }
 
+// utf8.EncodeRune of r, packed low byte first; *nb: its length
+__device__ __forceinline__ uint32_t pack_rune(uint32_t r, uint32_t* nb) {
+  if (r < 0x80) { *nb = 1; return r; }
+  if (r < 0x800) { *nb = 2; return (0xC0 | (r >> 6)) | ((0x80 | (r & 0x3F)) << 8); }
+  if (r < 0x10000) {
+    *nb = 3;
+    return (0xE0 | (r >> 12)) | ((0x80 | ((r >> 6) & 0x3F)) << 8) | ((0x80 | (r & 0x3F)) << 16);
+  }
+  *nb = 4;
+  return (0xF0 | (r >> 18)) | ((0x80 | ((r >> 12) & 0x3F)) << 8) | ((0x80 | ((r >> 6) & 0x3F)) << 16) |
+         ((0x80 | (r & 0x3F)) << 24);
+}
+
+__device__ inline bool hex4(const uint8_t* s, uint64_t p, uint64_t end, uint32_t* r) {
+  if (p + 4 > end) return false;
+  uint32_t v = 0;
+  for (int k = 0; k < 4; ++k) {
+    const int d = hexval(s[p + k]);
+    if (d < 0) return false;
+    v = (v << 4) | uint32_t(d);
+  }
+  *r = v;
+  return true;
+}
+
+// One unit of a JSON string body at s[i], i < end (the caller has dealt with
+// '"' and bytes < 0x20): a plain byte, an escape, or a raw rune. Returns the
+// index after it (UINT64_MAX if malformed); *w: the decoded UTF-8 bytes packed
+// low byte first, *nb: how many. As encoding/json (decode.go unquoteBytes):
+// a \u high surrogate followed by a \u low surrogate pairs up, any other
+// surrogate escape is U+FFFD and consumes nothing after itself; a raw byte
+// >= 0x80 goes through utf8.DecodeRune, so every byte of an invalid or
+// truncated sequence is U+FFFD on its own (1 byte in, 3 bytes out). A
+// continuation byte is 0x80..0xBF, so a sequence never reaches over the
+// closing quote; `end` (the line's '\n') bounds the reads.
+__device__ inline uint64_t json_unit(const uint8_t* s, uint64_t i, uint64_t end, uint32_t* w, uint32_t* nb) {
+  const uint32_t b = s[i];
+  if (b == '\\') {
+    if (i + 1 >= end) return UINT64_MAX;
+    const uint32_t e = s[i + 1];
+    i += 2;
+    *nb = 1;
+    switch (e) {
+      case '"': case '\\': case '/': *w = e; return i;
+      case 'b': *w = 8; return i;
+      case 'f': *w = 12; return i;
+      case 'n': *w = 10; return i;
+      case 'r': *w = 13; return i;
+      case 't': *w = 9; return i;
+      case 'u': break;
+      default: return UINT64_MAX;
+    }
+    uint32_t r;
+    if (!hex4(s, i, end, &r)) return UINT64_MAX;
+    i += 4;
+    if (r >= 0xD800 && r < 0xDC00) {
+      uint32_t r2;
+      if (i + 1 < end && s[i] == '\\' && s[i + 1] == 'u' && hex4(s, i + 2, end, &r2) && r2 >= 0xDC00 && r2 < 0xE000) {
+        i += 6;
+        r = 0x10000 + ((r - 0xD800) << 10) + (r2 - 0xDC00);
+      } else {
+        r = 0xFFFD;
+      }
+    } else if (r >= 0xDC00 && r < 0xE000) {
+      r = 0xFFFD;
+    }
+    *w = pack_rune(r, nb);
+    return i;
+  }
+  if (b < 0x80) {
+    *w = b;
+    *nb = 1;
+    return i + 1;
+  }
+  // utf8.DecodeRune: first byte -> length and the second byte's range
+  uint32_t need = 0, lo = 0x80, hi = 0xBF;
+  if (b >= 0xC2 && b <= 0xDF) need = 2;
+  else if (b >= 0xE0 && b <= 0xEF) { need = 3; if (b == 0xE0) lo = 0xA0; if (b == 0xED) hi = 0x9F; }
+  else if (b >= 0xF0 && b <= 0xF4) { need = 4; if (b == 0xF0) lo = 0x90; if (b == 0xF4) hi = 0x8F; }
+  bool ok = need != 0 && i + need <= end;
+  uint32_t v = b;
+  if (ok) {
+    const uint32_t c = s[i + 1];
+    ok = c >= lo && c <= hi;
+    v |= c << 8;
+  }
+  for (uint32_t k = 2; ok && k < need; ++k) {
+    const uint32_t c = s[i + k];
+    ok = c >= 0x80 && c <= 0xBF;
+    v |= c << (8 * k);
+  }
+  if (!ok) {
+    *w = 0xBDBFEFu;  // U+FFFD
+    *nb = 3;
+    return i + 1;
+  }
+  *w = v;
+  *nb = need;
+  return i + need;
+}
+
 // Decodes the JSON string starting after its opening quote at s[i]; returns
 // the index after the closing quote (or UINT64_MAX if malformed). WRITE:
 // raw bytes go to out. *olen: raw length; *h: FNV-1a 64 of the raw bytes.
+// *plain is cleared if the raw bytes are not the input bytes themselves (an
+// escape, or a byte coerced to U+FFFD); it is never set.
 template <bool WRITE>
 __device__ uint64_t json_string(const uint8_t* s, uint64_t i, uint64_t end, uint8_t* out, uint64_t* olen,
-                                uint64_t* h) {
+                                uint64_t* h, bool* plain) {
   uint64_t o = 0, hh = 1469598103934665603ull;
   auto put = [&](uint32_t b) {
     if (WRITE) out[o] = uint8_t(b);
     ++o;
     hh = (hh ^ b) * 1099511628211ull;
-  };
-  auto put_rune = [&](uint32_t r) {
-    if (r < 0x80) put(r);
-    else if (r < 0x800) { put(0xC0 | (r >> 6)); put(0x80 | (r & 0x3F)); }
-    else if (r < 0x10000) { put(0xE0 | (r >> 12)); put(0x80 | ((r >> 6) & 0x3F)); put(0x80 | (r & 0x3F)); }
-    else { put(0xF0 | (r >> 18)); put(0x80 | ((r >> 12) & 0x3F)); put(0x80 | ((r >> 6) & 0x3F)); put(0x80 | (r & 0x3F)); }
-  };
-  auto hex4 = [&](uint64_t p, uint32_t* r) -> bool {
-    if (p + 4 > end) return false;
-    uint32_t v = 0;
-    for (int k = 0; k < 4; ++k) {
-      const int d = hexval(s[p + k]);
-      if (d < 0) return false;
-      v = (v << 4) | uint32_t(d);
-    }
-    *r = v;
-    return true;
   };
   while (i < end) {
     const uint32_t b = s[i];
@@ -72,43 +165,17 @@ __device__ uint64_t json_string(const uint8_t* s, uint64_t i, uint64_t end, uint
       return i + 1;
     }
     if (b < 0x20) return UINT64_MAX;
-    if (b != '\\') {
+    if (b != '\\' && b < 0x80) {
       put(b);
       ++i;
       continue;
     }
-    if (i + 1 >= end) return UINT64_MAX;
-    const uint32_t e = s[i + 1];
-    i += 2;
-    switch (e) {
-      case '"': case '\\': case '/': put(e); break;
-      case 'b': put(8); break;
-      case 'f': put(12); break;
-      case 'n': put(10); break;
-      case 'r': put(13); break;
-      case 't': put(9); break;
-      case 'u': {
-        uint32_t r;
-        if (!hex4(i, &r)) return UINT64_MAX;
-        i += 4;
-        if (r >= 0xD800 && r < 0xDC00) {
-          // encoding/json: a high surrogate followed by \u low surrogate pairs up;
-          // any other lone surrogate decodes to U+FFFD
-          uint32_t r2;
-          if (i + 1 < end && s[i] == '\\' && s[i + 1] == 'u' && hex4(i + 2, &r2) && r2 >= 0xDC00 && r2 < 0xE000) {
-            i += 6;
-            r = 0x10000 + ((r - 0xD800) << 10) + (r2 - 0xDC00);
-          } else {
-            r = 0xFFFD;
-          }
-        } else if (r >= 0xDC00 && r < 0xE000) {
-          r = 0xFFFD;
-        }
-        put_rune(r);
-        break;
-      }
-      default: return UINT64_MAX;
-    }
+    uint32_t w, nb;
+    const uint64_t ni = json_unit(s, i, end, &w, &nb);
+    if (ni == UINT64_MAX) return UINT64_MAX;
+    if (ni - i != nb) *plain = false;  // an escape is longer than its bytes, a coerced byte shorter
+    for (uint32_t k = 0; k < nb; ++k) put((w >> (8 * k)) & 0xFFu);
+    i = ni;
   }
   return UINT64_MAX;
 }
@@ -120,16 +187,18 @@ __device__ inline bool lit(const uint8_t* s, uint64_t i, uint64_t end, const cha
 }
 
 // Parses line [a, e) (e = its '\n'). Fills key/value raw extents in the
-// decoded sense: returns false if malformed.
+// decoded sense: returns false if malformed. *plain: both strings' raw bytes
+// are their input bytes (the line is its frame around two byte ranges).
 template <bool WRITE>
 __device__ bool parse_line(const uint8_t* s, uint64_t a, uint64_t e, uint8_t* out, uint64_t* klen, uint64_t* vlen,
-                           uint64_t* kh) {
+                           uint64_t* kh, bool* plain) {
+  *plain = true;
   if (!lit(s, a, e, "{\"Key\":\"")) return false;
   uint64_t vh;
-  uint64_t i = json_string<WRITE>(s, a + 8, e, out, klen, kh);
+  uint64_t i = json_string<WRITE>(s, a + 8, e, out, klen, kh, plain);
   if (i == UINT64_MAX || !lit(s, i, e, ",\"Value\":\"")) return false;
   if (WRITE) out[*klen] = ' ';
-  i = json_string<WRITE>(s, i + 10, e, WRITE ? out + *klen + 1 : nullptr, vlen, &vh);
+  i = json_string<WRITE>(s, i + 10, e, WRITE ? out + *klen + 1 : nullptr, vlen, &vh, plain);
   if (i == UINT64_MAX || !lit(s, i, e, "}") || i + 1 != e) return false;
   if (WRITE) out[*klen + 1 + *vlen] = '\n';
   return true;
@@ -138,54 +207,75 @@ __device__ bool parse_line(const uint8_t* s, uint64_t a, uint64_t e, uint8_t* ou
 
 __global__ __launch_bounds__(kRT) void measure_kernel(const uint8_t* s, const uint64_t* nl, uint64_t nlines,
                                                       uint64_t* klen, uint64_t* vlen, uint64_t* kh, uint32_t* idx,
-                                                      unsigned long long* bad) {
+                                                      uint8_t* plain, unsigned long long* bad) {
   for (uint64_t j = uint64_t(blockIdx.x) * kRT + threadIdx.x; j < nlines; j += uint64_t(gridDim.x) * kRT) {
     const uint64_t a = j ? nl[j - 1] + 1 : 0, e = nl[j];
-    if (!parse_line<false>(s, a, e, nullptr, &klen[j], &vlen[j], &kh[j])) {
+    bool pl;
+    if (!parse_line<false>(s, a, e, nullptr, &klen[j], &vlen[j], &kh[j], &pl)) {
       atomicMin(bad, (unsigned long long)j);
       klen[j] = vlen[j] = 0;
       kh[j] = 0;
     }
+    plain[j] = uint8_t(pl);
     idx[j] = uint32_t(j);
   }
 }
 
+// The decoded bytes of a (valid) key, one at a time.
+struct KeyBytes {
+  const uint8_t* s;
+  uint64_t i, end;
+  uint32_t w = 0, nb = 0;
+  __device__ KeyBytes(const uint8_t* s_, uint64_t i_, uint64_t end_) : s(s_), i(i_), end(end_) {}
+  __device__ uint32_t next() {
+    if (nb == 0) i = json_unit(s, i, end, &w, &nb);
+    const uint32_t b = w & 0xFFu;
+    w >>= 8;
+    --nb;
+    return b;
+  }
+};
+
 // keep[line] = 1 unless an earlier line of the same equal-hash run has the
-// identical raw key (compared by decoding both); sorted order by (hash, line)
+// identical raw key; sorted order by (hash, line). Equal escaped bytes mean
+// equal keys (what json.Encoder writes is canonical, so its duplicates stop
+// there); spellings that differ -- a hex escape for an ASCII byte, \/ for /,
+// an escaped beside a raw rune, an invalid byte beside U+FFFD -- are decided
+// on the decoded bytes, both keys decoded a unit at a time, whatever their
+// length. With a malformed line in the input nothing is kept (and so nothing
+// decoded again or written, whatever the malformed lines hold): the call fails.
 __global__ __launch_bounds__(kRT) void dedupe_kernel(const uint8_t* s, const uint64_t* nl, const uint64_t* h_sorted,
                                                      const uint32_t* idx_sorted, uint64_t nlines, const uint64_t* klen,
-                                                     uint64_t* out_len, const uint64_t* vlen) {
+                                                     uint64_t* out_len, const uint64_t* vlen,
+                                                     const unsigned long long* bad) {
+  const bool any_bad = *bad != ~0ull;
   for (uint64_t q = uint64_t(blockIdx.x) * kRT + threadIdx.x; q < nlines; q += uint64_t(gridDim.x) * kRT) {
     const uint32_t j = idx_sorted[q];
-    bool keep = true;
+    bool keep = !any_bad;
     for (uint64_t p = q; keep && p-- > 0 && h_sorted[p] == h_sorted[q];) {
       const uint32_t k = idx_sorted[p];
+      // Equal 64-bit hashes of different keys: no test can construct two such
+      // keys, so this `continue` and the `same = false` of the decoded compare
+      // below are covered by reading alone.
       if (klen[k] != klen[j]) continue;
-      // byte compare of the two raw keys: decode both a byte at a time
       const uint64_t aj = j ? nl[j - 1] + 1 : 0, ak = k ? nl[k - 1] + 1 : 0;
-      uint8_t bj[64], bk[64];
-      uint64_t lj, lk, hj, hk;
-      // keys longer than 64 raw bytes: compare the escaped forms instead --
-      // json.Encoder output is canonical, so equal raw keys have equal escapes
-      if (klen[j] <= 64) {
-        json_string<true>(s, aj + 8, nl[j], bj, &lj, &hj);
-        json_string<true>(s, ak + 8, nl[k], bk, &lk, &hk);
-        bool same = true;
-        for (uint64_t t = 0; t < lj && same; ++t) same = bj[t] == bk[t];
-        if (same) keep = false;
-      } else {
-        bool same = true;
-        for (uint64_t t = 8;; ++t) {
-          const uint8_t x = s[aj + t], y = s[ak + t];
-          if (x != y) { same = false; break; }
-          if (x == '"') break;  // the closing quote (escaped ones are skipped below)
-          if (x == '\\') {
-            ++t;
-            if (s[aj + t] != s[ak + t]) { same = false; break; }
-          }
+      bool same = true;
+      for (uint64_t t = 8;; ++t) {
+        const uint8_t x = s[aj + t], y = s[ak + t];
+        if (x != y) { same = false; break; }
+        if (x == '"') break;  // the closing quote (escaped ones are skipped below)
+        if (x == '\\') {
+          ++t;
+          if (s[aj + t] != s[ak + t]) { same = false; break; }
         }
-        if (same) keep = false;
       }
+      if (!same) {  // another spelling of the same key? (equal hash and length: almost surely)
+        KeyBytes cj(s, aj + 8, nl[j]), ck(s, ak + 8, nl[k]);
+        same = true;
+        for (uint64_t t = 0; t < klen[j]; ++t)
+          if (cj.next() != ck.next()) { same = false; break; }
+      }
+      if (same) keep = false;
     }
     out_len[j] = keep ? klen[j] + 1 + vlen[j] + 1 : 0;
   }
@@ -273,19 +363,23 @@ __global__ void nl_total_kernel(const uint64_t* offs, const uint64_t* counts, ui
 // ---- writer: one WAVE per 64 kept lines ----------------------------------
 // Lane l fetches line j0 + l's extents, then the wave walks the 64 lines and
 // lane l builds output dwords (pos >> 2) + l + 64k of `key value\n`. A line
-// with no escape in it (encoded length == 21 + raw key + raw value: the
-// `{"Key":"`, `","Value":"`, `"}` frame) is a copy of two byte ranges: a dword
-// wholly inside one range is one unaligned read (two aligned dwords +
-// v_alignbyte); a line with escapes is decoded by its own lane (parse_line).
+// that measure_kernel flagged plain (no escape and no coerced byte in either
+// string, so its encoded length is 21 + raw key + raw value: the `{"Key":"`,
+// `","Value":"`, `"}` frame) is a copy of two byte ranges: a dword wholly
+// inside one range is one unaligned read (two aligned dwords + v_alignbyte);
+// any other line is decoded by its own lane (parse_line). The lengths alone
+// cannot tell the two apart: a coerced byte adds the two bytes that two
+// short escapes take away.
 __global__ __launch_bounds__(kRT) void write_kernel(const uint8_t* s, uint64_t n, const uint64_t* nl, uint64_t nlines,
                                                     const uint64_t* klen, const uint64_t* vlen,
-                                                    const uint64_t* out_len, const uint64_t* pos, uint8_t* out,
-                                                    uint64_t out_cap) {
+                                                    const uint8_t* plain, const uint64_t* out_len,
+                                                    const uint64_t* pos, uint8_t* out, uint64_t out_cap) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t nwaves = uint64_t(gridDim.x) * (kRT / 64);
   for (uint64_t j0 = (uint64_t(blockIdx.x) * (kRT / 64) + (threadIdx.x >> 6)) * 64u; j0 < nlines; j0 += nwaves * 64u) {
     const uint64_t jm = j0 + lane;
     uint64_t a = 0, e = 0, kl = 0, vl = 0, ol = 0, P = 0;
+    int pl = 0;
     if (jm < nlines) {
       a = jm ? nl[jm - 1] + 1 : 0;
       e = nl[jm];
@@ -293,6 +387,7 @@ __global__ __launch_bounds__(kRT) void write_kernel(const uint8_t* s, uint64_t n
       P = pos[jm];
       kl = klen[jm];
       vl = vlen[jm];
+      pl = plain[jm];
     }
     const uint32_t cnt = uint32_t(min(uint64_t(64), nlines - j0));
     for (uint32_t r = 0; r < cnt; ++r) {
@@ -300,10 +395,11 @@ __global__ __launch_bounds__(kRT) void write_kernel(const uint8_t* s, uint64_t n
       if (!olr || Pr + olr > out_cap) continue;
       const uint64_t ar = __shfl(a, int(r), 64), er = __shfl(e, int(r), 64);
       const uint64_t klr = __shfl(kl, int(r), 64), vlr = __shfl(vl, int(r), 64);
-      if (er - ar != 21u + klr + vlr) {  // escapes inside: decoded by the line's lane
+      if (!__shfl(pl, int(r), 64)) {  // escapes or coerced bytes inside: decoded by the line's lane
         if (lane == r) {
           uint64_t x, y, h;
-          parse_line<true>(s, a, e, out + P, &x, &y, &h);
+          bool f;
+          parse_line<true>(s, a, e, out + P, &x, &y, &h, &f);
         }
         continue;
       }
@@ -378,7 +474,7 @@ hipError_t reduce_lines(const uint8_t* d_in, uint64_t n, uint64_t nlines, void* 
       hipSuccess)
     return e;
   const size_t tmp = std::max({sel_tmp, sort_tmp, scan_tmp});
-  const size_t need = a256(L * 8) * 7 + a256(L * 4) * 2 + a256(tmp) + 2 * a256(nblk * 8);
+  const size_t need = a256(L * 8) * 7 + a256(L * 4) * 2 + a256(L) + a256(tmp) + 2 * a256(nblk * 8);
   if (!scratch || *scratch_bytes < need) {
     *scratch_bytes = need;
     return hipSuccess;
@@ -398,6 +494,7 @@ hipError_t reduce_lines(const uint8_t* d_in, uint64_t n, uint64_t nlines, void* 
   uint64_t* pos = reinterpret_cast<uint64_t*>(take(L * 8));
   uint32_t* idx = reinterpret_cast<uint32_t*>(take(L * 4));
   uint32_t* idx_sorted = reinterpret_cast<uint32_t*>(take(L * 4));
+  uint8_t* plain = take(L);
   void* t = take(tmp);
   uint64_t* blk_cnt = reinterpret_cast<uint64_t*>(take(nblk * 8));
   uint64_t* blk_off = reinterpret_cast<uint64_t*>(take(nblk * 8));
@@ -416,18 +513,18 @@ hipError_t reduce_lines(const uint8_t* d_in, uint64_t n, uint64_t nlines, void* 
   hipLaunchKernelGGL(nl_total_kernel, dim3(1), dim3(1), 0, s, blk_off, blk_cnt, nblk, d_info);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(measure_kernel, dim3(grid_of(nlines)), dim3(kRT), 0, s, d_in, nl, nlines, klen, vlen, kh, idx,
-                     reinterpret_cast<unsigned long long*>(d_info + 1));
+                     plain, reinterpret_cast<unsigned long long*>(d_info + 1));
   if ((e = hipGetLastError()) != hipSuccess) return e;
   tb = tmp;
   if ((e = hipcub::DeviceRadixSort::SortPairs(t, tb, kh, kh_sorted, idx, idx_sorted, nlines, 0, 64, s)) != hipSuccess)
     return e;
   hipLaunchKernelGGL(dedupe_kernel, dim3(grid_of(nlines)), dim3(kRT), 0, s, d_in, nl, kh_sorted, idx_sorted, nlines,
-                     klen, out_len, vlen);
+                     klen, out_len, vlen, reinterpret_cast<const unsigned long long*>(d_info + 1));
   if ((e = hipGetLastError()) != hipSuccess) return e;
   tb = tmp;
   if ((e = hipcub::DeviceScan::ExclusiveSum(t, tb, out_len, pos, nlines, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(write_kernel, dim3(std::min<uint64_t>((nlines + 255) / 256, 4096)), dim3(kRT), 0, s, d_in, n, nl,
-                     nlines, klen, vlen, out_len, pos, out, out_cap);
+                     nlines, klen, vlen, plain, out_len, pos, out, out_cap);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(total_kernel, dim3(1), dim3(1), 0, s, pos, out_len, nlines, d_info + 2);
   return hipGetLastError();

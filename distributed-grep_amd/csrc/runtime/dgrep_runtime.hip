@@ -1845,7 +1845,7 @@ extern "C" int dgrep_reduce(dgrep_ctx* c, const uint8_t* data, size_t n, dgrep_r
     HIPCHK(hipMemcpyAsync(info, d_info, sizeof info, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (info[1] != UINT64_MAX) {
-      c->err = "reduce input line " + std::to_string(info[1] + 1) + " is not a json.Encoder KeyValue line";
+      c->err = "reduce input line " + std::to_string(info[1] + 1) + " is not a {\"Key\":\"..\",\"Value\":\"..\"} line";
       return DGREP_E_INVALID;
     }
     if (info[2] <= c->red_out_cap) break;

@@ -188,9 +188,18 @@ int dgrep_last_encode_ms(dgrep_ctx* ctx, float* ms);
  * readReduceInput decodes them); the result is one "key value\n" line
  * (fmt "%v %v\n" of the raw strings) per distinct key with one of its values
  * (the grep Reduce returns values[0] after an unstable sort, so any value of
- * a duplicated key is a valid result), in input order of the kept lines (the
- * reference writes them in Go map order, i.e. unordered). A line that is not a
- * json.Encoder KeyValue line fails with DGREP_E_INVALID (never guessed). */
+ * a duplicated key is a valid result): here the value of the key's FIRST
+ * line, in input order of the kept lines (the reference writes them in Go map
+ * order, i.e. unordered). Accepted is the compact two-field form
+ * {"Key":"<json string>","Value":"<json string>"}\n byte for byte, with any
+ * JSON string encoding/json's decoder accepts -- not only json.Encoder's
+ * canonical spelling: \/ and \uXXXX in either hex case, escaped or raw runes,
+ * and raw invalid UTF-8, each byte of which becomes U+FFFD as in the decoder.
+ * Keys are compared decoded, so two spellings of one key are one key. Every
+ * other line -- whitespace, other field order or names, a third field, a last
+ * line without '\n', even where the decoder would take it -- fails the call
+ * with DGREP_E_INVALID (never guessed); dgrep_last_error names the first such
+ * line. */
 typedef struct {
   uint64_t lines_in; /* KeyValue lines read */
   uint64_t total;    /* output bytes */

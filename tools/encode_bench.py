@@ -83,7 +83,7 @@ def main():
         "records_per_s": round(cnt / (best * 1e-3)), "output_gbs": round(total / (best * 1e-3) / 1e9, 2),
         "cpu_oracle_records_per_s_1core": round(2000 / cpu_s),
         "checked": "first 2,000 records bit-exact vs oracle per partition prefix",
-        "reduce_ms_best": round(min(red_ms), 3), "reduce_lines_per_s": round(cnt / (min(red_ms) * 1e-3)),
+        "reduce_ms_best": round(min(red_ms), 3), "reduce_ms_all": [round(x, 3) for x in red_ms], "reduce_lines_per_s": round(cnt / (min(red_ms) * 1e-3)),
         "reduce_output_bytes": len(red_out)}), flush=True)
     ctx.close()
 
