@@ -22,6 +22,7 @@
 #include "../../../include/dgrep_blob.h"
 #include "../kernels/batch.h"
 #include "../kernels/encode.h"
+#include "../kernels/encode_batch.h"
 #include "../kernels/reduce.h"
 #include "../kernels/scan_common.h"
 #include "../kernels/synth.h"
@@ -226,6 +227,11 @@ struct dgrep_ctx {
   uint64_t res_sbegin_cap = 0;
   hipEvent_t evb0 = nullptr, evb1 = nullptr, evb2 = nullptr, evb3 = nullptr;
   float last_newline_ms = 0.f, last_rebase_ms = 0.f;
+  // partition writer over a batch (dgrep_map_partitions_batch / dgrep_encode_batch_device)
+  uint8_t* d_bat_names = nullptr;  // the filename table: offsets [k + 1], hash states [k], escaped names
+  uint64_t bat_names_cap = 0;
+  uint64_t* d_bat_cells = nullptr;  // [k * nreduce + 1]
+  uint64_t bat_cells_cap = 0;
 
   // reduce task (dgrep_reduce)
   uint8_t* d_red_scratch = nullptr;
@@ -553,7 +559,7 @@ extern "C" void dgrep_close(dgrep_ctx* c) {
                   c->d_pend, c->d_long_tbl, c->d_st2id, c->d_seg, c->d_seg_off, c->d_segmap, c->d_seg_from, c->d_seg_state, c->d_tiles, c->d_out_off, c->d_line_base, c->d_staging, c->d_counters,
                   c->d_overflow, c->d_data, c->d_res_line, c->d_res_start, c->d_res_len, c->d_enc_scratch,
                   c->d_fname, c->d_bounds, c->d_enc_out, c->d_red_scratch, c->d_red_out, c->d_bat_begin,
-                  c->d_bat_lines, c->d_bat_sums, c->d_res_split, c->d_res_sbegin};
+                  c->d_bat_lines, c->d_bat_sums, c->d_res_split, c->d_res_sbegin, c->d_bat_names, c->d_bat_cells};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
@@ -1634,6 +1640,36 @@ static int ingest_packed(dgrep_ctx* c, const uint8_t* const* data, const size_t*
   return DGREP_OK;
 }
 
+// Host splits -> packed ingest -> batch scan into the context's result arrays
+// (d_res_line / start / len / split, and d_res_sbegin when `ranges`), grown and
+// re-scanned once if the first guess at the record count was too small.
+static int batch_scan_host(dgrep_ctx* c, const uint8_t* const* data, const size_t* n, size_t nsplits, size_t total,
+                           bool ranges, uint64_t* count_out) {
+  int rc;
+  static_assert(sizeof(size_t) == sizeof(uint64_t), "split lengths are passed on as u64");
+  if ((rc = batch_setup(c, reinterpret_cast<const uint64_t*>(n), nsplits)) != DGREP_OK) return rc;
+  if (total) {
+    uint64_t cap = c->data_cap;
+    if ((rc = grow(c, &c->d_data, &cap, (uint64_t(total) + 63) & ~uint64_t(63))) != DGREP_OK) return rc;
+    c->data_cap = cap;
+    if ((rc = ingest_packed(c, data, n, nsplits, total)) != DGREP_OK) return rc;
+  }
+  if (ranges && (rc = grow(c, &c->d_res_sbegin, &c->res_sbegin_cap, uint64_t(nsplits) + 1)) != DGREP_OK) return rc;
+  uint64_t want = std::max<uint64_t>(c->res_cap, std::max<uint64_t>(1024, total / 512));
+  uint64_t count = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if ((rc = grow_results(c, want)) != DGREP_OK) return rc;
+    if ((rc = grow(c, &c->d_res_split, &c->res_split_cap, c->res_cap)) != DGREP_OK) return rc;
+    if ((rc = batch_resident(c, c->d_data, total, nsplits, c->d_res_line, c->d_res_start, c->d_res_len, c->d_res_split,
+                             ranges ? c->d_res_sbegin : nullptr, c->res_cap, &count, attempt == 0)) != DGREP_OK)
+      return rc;
+    if (count <= c->res_cap) break;
+    want = count;
+  }
+  *count_out = count;
+  return DGREP_OK;
+}
+
 extern "C" int dgrep_scan_batch(dgrep_ctx* c, const uint8_t* const* data, const size_t* n, size_t nsplits,
                                 dgrep_batch_result* out) {
   if (out) memset(out, 0, sizeof *out);
@@ -1648,26 +1684,8 @@ extern "C" int dgrep_scan_batch(dgrep_ctx* c, const uint8_t* const* data, const 
   if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
   HIPCHK(hipSetDevice(c->device));
   int rc;
-  static_assert(sizeof(size_t) == sizeof(uint64_t), "split lengths are passed on as u64");
-  if ((rc = batch_setup(c, reinterpret_cast<const uint64_t*>(n), nsplits)) != DGREP_OK) return rc;
-  if (total) {
-    uint64_t cap = c->data_cap;
-    if ((rc = grow(c, &c->d_data, &cap, (uint64_t(total) + 63) & ~uint64_t(63))) != DGREP_OK) return rc;
-    c->data_cap = cap;
-    if ((rc = ingest_packed(c, data, n, nsplits, total)) != DGREP_OK) return rc;
-  }
-  if ((rc = grow(c, &c->d_res_sbegin, &c->res_sbegin_cap, uint64_t(nsplits) + 1)) != DGREP_OK) return rc;
-  uint64_t want = std::max<uint64_t>(c->res_cap, std::max<uint64_t>(1024, total / 512));
   uint64_t count = 0;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    if ((rc = grow_results(c, want)) != DGREP_OK) return rc;
-    if ((rc = grow(c, &c->d_res_split, &c->res_split_cap, c->res_cap)) != DGREP_OK) return rc;
-    if ((rc = batch_resident(c, c->d_data, total, nsplits, c->d_res_line, c->d_res_start, c->d_res_len, c->d_res_split,
-                             c->d_res_sbegin, c->res_cap, &count, attempt == 0)) != DGREP_OK)
-      return rc;
-    if (count <= c->res_cap) break;
-    want = count;
-  }
+  if ((rc = batch_scan_host(c, data, n, nsplits, total, true, &count)) != DGREP_OK) return rc;
   out->count = count;
   out->nsplits = nsplits;
   out->split_begin = static_cast<uint64_t*>(malloc((nsplits + 1) * 8));
@@ -1808,6 +1826,195 @@ extern "C" void dgrep_partitions_free(dgrep_partitions* p) {
   if (!p) return;
   free(p->begin);
   free(p->end);
+  free(p->bytes);
+  memset(p, 0, sizeof *p);
+}
+
+// ---- partition + intermediate writer over a batch (kernels/encode_batch.h) ----
+// The host image of the device filename table: name_off [k + 1] u64, then the
+// FNV-1a prefix states [k] u32, then every name JSON-escaped, concatenated.
+static int build_name_table(dgrep_ctx* c, const char* const* filename, const size_t* fn, size_t k,
+                            std::vector<uint8_t>* img) {
+  const size_t off_bytes = (k + 1) * 8, hash_bytes = k * 4;
+  std::vector<uint64_t> off(k + 1);
+  std::vector<uint32_t> hash(k);
+  std::vector<uint8_t> esc;
+  img->assign(off_bytes + hash_bytes, 0);
+  for (size_t i = 0; i < k; ++i) {
+    const uint8_t* f = reinterpret_cast<const uint8_t*>(filename[i]);
+    if (fn[i] >= (size_t(1) << 31)) { c->err = "filename too long"; return DGREP_E_INVALID; }
+    off[i] = img->size() - off_bytes - hash_bytes;
+    hash[i] = key_prefix_hash(f, fn[i]);
+    size_t plain = 0;  // the usual name has nothing to escape: copied as it is
+    while (plain < fn[i] && f[plain] >= 0x20 && f[plain] < 0x80 && f[plain] != '"' && f[plain] != '\\' &&
+           f[plain] != '<' && f[plain] != '>' && f[plain] != '&')
+      ++plain;
+    if (plain == fn[i]) {
+      img->insert(img->end(), f, f + fn[i]);
+      continue;
+    }
+    const uint64_t fj = json_escape_host(f, fn[i], nullptr);
+    if (fj >= (uint64_t(1) << 31)) { c->err = "filename too long"; return DGREP_E_INVALID; }
+    esc.resize(fj);
+    json_escape_host(f, fn[i], esc.data());
+    img->insert(img->end(), esc.begin(), esc.end());
+  }
+  off[k] = img->size() - off_bytes - hash_bytes;
+  memcpy(img->data(), off.data(), off_bytes);
+  memcpy(img->data() + off_bytes, hash.data(), hash_bytes);
+  return DGREP_OK;
+}
+
+// Records of a batch scan over P (n bytes at d_packed, k splits, begin[] in
+// c->bat_begin) -> every cell's lines in d_out; cell_off (host, k * nreduce + 1).
+static int encode_batch_resident(dgrep_ctx* c, const uint8_t* d_packed, uint64_t n, uint64_t k, const uint64_t* d_line,
+                                 const uint64_t* d_start, const uint64_t* d_len, const uint32_t* d_split,
+                                 uint64_t count, const std::vector<uint8_t>& names, uint32_t nreduce, uint8_t* d_out,
+                                 uint64_t out_cap, uint64_t* cell_off, uint64_t* total) {
+  const uint64_t cells = k * uint64_t(nreduce);
+  *total = 0;
+  if (count == 0) {
+    memset(cell_off, 0, (cells + 1) * 8);
+    c->last_encode_ms = 0.f;
+    return DGREP_OK;
+  }
+  int rc;
+  if ((rc = grow(c, &c->d_bat_names, &c->bat_names_cap, names.size())) != DGREP_OK) return rc;
+  if ((rc = grow(c, &c->d_bat_cells, &c->bat_cells_cap, cells + 1)) != DGREP_OK) return rc;
+  HIPCHK(hipMemcpyAsync(c->d_bat_begin, c->bat_begin.data(), (k + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_bat_names, names.data(), names.size(), hipMemcpyHostToDevice, c->stream));
+  EncodeBatchArgs a;
+  a.data = d_packed;
+  a.n = n;
+  a.begin = c->d_bat_begin;
+  a.k = k;
+  a.line_no = d_line;
+  a.start = d_start;
+  a.len = d_len;
+  a.split = d_split;
+  a.count = count;
+  a.name_off = reinterpret_cast<const uint64_t*>(c->d_bat_names);
+  a.name_hash = reinterpret_cast<const uint32_t*>(c->d_bat_names + (k + 1) * 8);
+  a.names = c->d_bat_names + (k + 1) * 8 + k * 4;
+  a.nreduce = nreduce;
+  size_t need = 0;
+  HIPCHK(encode_batch(a, nullptr, &need, nullptr, 0, nullptr, c->stream));
+  if ((rc = grow(c, &c->d_enc_scratch, &c->enc_scratch_cap, need)) != DGREP_OK) return rc;
+  size_t have = c->enc_scratch_cap;
+  HIPCHK(hipEventRecord(c->ev0, c->stream));
+  HIPCHK(encode_batch(a, c->d_enc_scratch, &have, d_out, out_cap, c->d_bat_cells, c->stream));
+  HIPCHK(hipEventRecord(c->ev1, c->stream));
+  HIPCHK(hipMemcpyAsync(cell_off, c->d_bat_cells, (cells + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->last_encode_ms, c->ev0, c->ev1));
+  *total = cell_off[cells];
+  return DGREP_OK;
+}
+
+// the argument checks the two batch-encode forms share (after their own)
+static int encode_batch_args(dgrep_ctx* c, const char* const* filename, const size_t* fn, size_t nsplits,
+                             uint32_t nreduce) {
+  if (!filename || !fn) return DGREP_E_INVALID;
+  if (nreduce == 0 || nreduce > 65535) { c->err = "nreduce must be 1..65535"; return DGREP_E_INVALID; }
+  for (size_t i = 0; i < nsplits; ++i)
+    if (fn[i] && !filename[i]) return DGREP_E_INVALID;
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_encode_batch_device(dgrep_ctx* c, const void* d_packed, size_t n_packed,
+                                         const uint64_t* split_len, size_t nsplits, const uint64_t* d_line_no,
+                                         const uint64_t* d_start, const uint64_t* d_len, const uint32_t* d_split,
+                                         uint64_t count, const char* const* filename, const size_t* fn,
+                                         uint32_t nreduce, void* d_out, uint64_t out_cap, uint64_t* cell_off,
+                                         uint64_t* total) {
+  if (total) *total = 0;
+  if (!c || !total || !cell_off || !split_len || nsplits == 0 || nsplits > UINT32_MAX || (n_packed && !d_packed) ||
+      (count && (!d_line_no || !d_start || !d_len || !d_split)) || (out_cap && !d_out))
+    return DGREP_E_INVALID;
+  int rc;
+  if ((rc = encode_batch_args(c, filename, fn, nsplits, nreduce)) != DGREP_OK) return rc;
+  uint64_t sum = nsplits - 1;
+  for (size_t i = 0; i < nsplits; ++i) {
+    if (split_len[i] > UINT64_MAX - 1 - sum) {
+      c->err = "dgrep_encode_batch_device: the split lengths overflow";
+      return DGREP_E_INVALID;
+    }
+    sum += split_len[i];
+  }
+  if (sum != n_packed) {
+    c->err = "dgrep_encode_batch_device: n_packed must be the split lengths plus nsplits - 1 separators";
+    return DGREP_E_INVALID;
+  }
+  if (uint64_t(nsplits) * nreduce >= (uint64_t(1) << 32)) {
+    c->err = "dgrep_encode_batch_device: nsplits * nreduce must be below 2^32 cells";
+    return DGREP_E_UNSUPPORTED;
+  }
+  if (count >= (uint64_t(1) << 32)) { c->err = "more than 2^32-1 records"; return DGREP_E_UNSUPPORTED; }
+  std::vector<uint8_t> names;
+  if ((rc = build_name_table(c, filename, fn, nsplits, &names)) != DGREP_OK) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  if ((rc = batch_setup(c, split_len, nsplits)) != DGREP_OK) return rc;
+  return encode_batch_resident(c, static_cast<const uint8_t*>(d_packed), n_packed, nsplits, d_line_no, d_start, d_len,
+                               d_split, count, names, nreduce, static_cast<uint8_t*>(d_out), out_cap, cell_off, total);
+}
+
+extern "C" int dgrep_map_partitions_batch(dgrep_ctx* c, const uint8_t* const* data, const size_t* n,
+                                          const char* const* filename, const size_t* fn, size_t nsplits,
+                                          uint32_t nreduce, dgrep_batch_partitions* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!c || !out || !data || !n || nsplits == 0 || nsplits > UINT32_MAX) return DGREP_E_INVALID;
+  int rc;
+  if ((rc = encode_batch_args(c, filename, fn, nsplits, nreduce)) != DGREP_OK) return rc;
+  for (size_t i = 0; i < nsplits; ++i)
+    if (n[i] && !data[i]) return DGREP_E_INVALID;
+  size_t total_in = 0;
+  if (!pack_total(n, nsplits, &total_in) || total_in == ~size_t(0)) {
+    c->err = "dgrep_map_partitions_batch: the split lengths overflow";
+    return DGREP_E_INVALID;
+  }
+  if (uint64_t(nsplits) * nreduce >= (uint64_t(1) << 32)) {
+    c->err = "dgrep_map_partitions_batch: nsplits * nreduce must be below 2^32 cells";
+    return DGREP_E_UNSUPPORTED;
+  }
+  if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
+  std::vector<uint8_t> names;
+  if ((rc = build_name_table(c, filename, fn, nsplits, &names)) != DGREP_OK) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  uint64_t count = 0;
+  if ((rc = batch_scan_host(c, data, n, nsplits, total_in, false, &count)) != DGREP_OK) return rc;
+  if (count >= (uint64_t(1) << 32)) { c->err = "more than 2^32-1 records"; return DGREP_E_UNSUPPORTED; }
+  const uint64_t cells = uint64_t(nsplits) * nreduce;
+  out->cell_off = static_cast<uint64_t*>(calloc(cells + 1, 8));
+  if (!out->cell_off) return DGREP_E_NOMEM;
+  uint64_t total = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if ((rc = encode_batch_resident(c, c->d_data, total_in, nsplits, c->d_res_line, c->d_res_start, c->d_res_len,
+                                    c->d_res_split, count, names, nreduce, c->d_enc_out, c->enc_out_cap,
+                                    out->cell_off, &total)) != DGREP_OK) {
+      dgrep_batch_partitions_free(out);
+      return rc;
+    }
+    if (total <= c->enc_out_cap) break;
+    if ((rc = grow(c, &c->d_enc_out, &c->enc_out_cap, total + total / 16)) != DGREP_OK) {
+      dgrep_batch_partitions_free(out);
+      return rc;
+    }
+  }
+  out->nsplits = nsplits;
+  out->nreduce = nreduce;
+  out->total = total;
+  if (total) {
+    out->bytes = static_cast<uint8_t*>(malloc(total));
+    if (!out->bytes) { dgrep_batch_partitions_free(out); return DGREP_E_NOMEM; }
+    HIPCHK(hipMemcpyAsync(out->bytes, c->d_enc_out, total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return DGREP_OK;
+}
+
+extern "C" void dgrep_batch_partitions_free(dgrep_batch_partitions* p) {
+  if (!p) return;
+  free(p->cell_off);
   free(p->bytes);
   memset(p, 0, sizeof *p);
 }

@@ -58,6 +58,7 @@ EXPORTS = (
     "dgrep_comm_unique_id", "dgrep_comm_open", "dgrep_comm_close", "dgrep_gather_records_device",
     "dgrep_gather_records", "dgrep_gathered_free", "dgrep_comm_last_error",
     "dgrep_scan_batch", "dgrep_batch_result_free", "dgrep_scan_batch_device", "dgrep_last_batch_ms",
+    "dgrep_map_partitions_batch", "dgrep_batch_partitions_free", "dgrep_encode_batch_device",
 )
 COMM_ID_BYTES = 128
 
@@ -109,6 +110,11 @@ class _BatchResult(ctypes.Structure):
                 ("start", ctypes.POINTER(ctypes.c_uint64)), ("len", ctypes.POINTER(ctypes.c_uint64)),
                 ("split", ctypes.POINTER(ctypes.c_uint32)), ("nsplits", ctypes.c_uint64),
                 ("split_begin", ctypes.POINTER(ctypes.c_uint64))]
+
+
+class _BatchPartitions(ctypes.Structure):
+    _fields_ = [("nsplits", ctypes.c_uint64), ("nreduce", ctypes.c_uint32), ("total", ctypes.c_uint64),
+                ("cell_off", ctypes.POINTER(ctypes.c_uint64)), ("bytes", ctypes.c_void_p)]
 
 
 class _BlobInfo(ctypes.Structure):
@@ -215,6 +221,14 @@ def lib() -> ctypes.CDLL:
             L.dgrep_scan_batch_device.restype = i
             L.dgrep_last_batch_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
             L.dgrep_last_batch_ms.restype = i
+            L.dgrep_map_partitions_batch.argtypes = [vp, vp, vp, vp, vp, sz, ctypes.c_uint32,
+                                                     ctypes.POINTER(_BatchPartitions)]
+            L.dgrep_map_partitions_batch.restype = i
+            L.dgrep_batch_partitions_free.argtypes = [ctypes.POINTER(_BatchPartitions)]
+            L.dgrep_batch_partitions_free.restype = None
+            L.dgrep_encode_batch_device.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp, u64, vp, vp, ctypes.c_uint32,
+                                                    vp, u64, vp, ctypes.POINTER(u64)]
+            L.dgrep_encode_batch_device.restype = i
             _lib = L
     return _lib
 
@@ -446,6 +460,53 @@ class Context:
                                                 len(fname), nreduce, ctypes.c_void_p(d_out), out_cap, b, e,
                                                 ctypes.byref(tot)))
         return list(b), list(e), int(tot.value)
+
+    def map_partitions_batch(self, files, nreduce: int) -> List[List[bytes]]:
+        """Map + writeMapOutput of many splits in one scan and one encode
+        (dgrep_map_partitions_batch): files = [(filename, contents), ...];
+        element [s][p] is the byte content of mr-<s>-<p>. No file: [] without a
+        C call."""
+        files = list(files)
+        if not files:
+            return []
+        as_bytes = lambda x: x.encode("utf-8", "surrogateescape") if isinstance(x, str) else bytes(x)
+        names = [as_bytes(f) for f, _ in files]
+        raws = [as_bytes(c) for _, c in files]
+        k = len(files)
+        bufs = [np.frombuffer(r, dtype=np.uint8) for r in raws]  # keep the bytes alive over the call
+        ptrs = (ctypes.c_void_p * k)(*[b.ctypes.data if len(b) else None for b in bufs])
+        lens = (ctypes.c_size_t * k)(*[len(r) for r in raws])
+        fptrs = (ctypes.c_char_p * k)(*names)
+        flens = (ctypes.c_size_t * k)(*[len(f) for f in names])
+        res = _BatchPartitions()
+        self._check(self._L.dgrep_map_partitions_batch(self._h, ptrs, lens, fptrs, flens, k, nreduce,
+                                                       ctypes.byref(res)))
+        try:
+            raw = ctypes.string_at(res.bytes, res.total) if res.total else b""
+            off = np.ctypeslib.as_array(res.cell_off, shape=(k * nreduce + 1,)).tolist()
+            return [[raw[off[s * nreduce + p]:off[s * nreduce + p + 1]] for p in range(nreduce)] for s in range(k)]
+        finally:
+            self._L.dgrep_batch_partitions_free(ctypes.byref(res))
+
+    def encode_batch_device(self, d_packed: int, n_packed: int, split_len, d_line: int, d_start: int, d_len: int,
+                            d_split: int, count: int, filenames, nreduce: int, d_out: int, out_cap: int):
+        """dgrep_encode_batch_device over the records dgrep_scan_batch_device
+        returned for the same packed buffer: returns (cell_off list of
+        len(split_len) * nreduce + 1 entries, total)."""
+        lens = np.ascontiguousarray(split_len, dtype=np.uint64)
+        k = len(lens)
+        names = [f.encode("utf-8", "surrogateescape") if isinstance(f, str) else bytes(f) for f in filenames]
+        assert len(names) == k, "one filename per split"
+        fptrs = (ctypes.c_char_p * max(k, 1))(*names)
+        flens = (ctypes.c_size_t * max(k, 1))(*[len(f) for f in names])
+        off = np.zeros(k * nreduce + 1, np.uint64)
+        tot = ctypes.c_uint64()
+        self._check(self._L.dgrep_encode_batch_device(
+            self._h, ctypes.c_void_p(d_packed), n_packed, ctypes.c_void_p(lens.ctypes.data if k else None), k,
+            ctypes.c_void_p(d_line), ctypes.c_void_p(d_start), ctypes.c_void_p(d_len), ctypes.c_void_p(d_split),
+            count, fptrs, flens, nreduce, ctypes.c_void_p(d_out or None), out_cap, ctypes.c_void_p(off.ctypes.data),
+            ctypes.byref(tot)))
+        return off.tolist(), int(tot.value)
 
     def reduce(self, data: bytes) -> bytes:
         """One grep reduce task on the GPU (dgrep_reduce): data = the

@@ -275,6 +275,60 @@ int dgrep_scan_batch_device(dgrep_ctx* ctx, const void* d_packed, size_t n_packe
  * per-split ranges + rebase of the records. */
 int dgrep_last_batch_ms(dgrep_ctx* ctx, float* newline_ms, float* rebase_ms);
 
+/* ---- whole map tasks over a batch: every split's intermediate files ---------
+ * A map task ends at its files mr-<task>-<p>, one per reduce partition
+ * (map_reduce/worker.go:78-109). The batch form of dgrep_map_partitions writes
+ * them for k splits with k filenames from one scan and one encode. Cell (s, p)
+ * holds the bytes of mr-<s>-<p>, exactly what dgrep_map_partitions(split s,
+ * filename s, nreduce) returns for partition p: Key = Sprintf("%s (line number
+ * #%v)", filename[s], line_no) with line_no counted within split s, partition
+ * = ihash(Key) % nreduce, lines in line order. Cells are contiguous,
+ * split-major, then partition: cell c = s * nreduce + p occupies
+ * bytes[cell_off[c] : cell_off[c+1]); cell_off has nsplits * nreduce + 1
+ * entries, cell_off[0] = 0, the last one = total; an empty cell has equal
+ * offsets. Filenames may have any length. */
+typedef struct {
+  uint64_t nsplits;
+  uint32_t nreduce;
+  uint64_t total;     /* bytes over all cells */
+  uint64_t* cell_off; /* nsplits * nreduce + 1 */
+  uint8_t* bytes;
+} dgrep_batch_partitions;
+
+/* Host splits and filenames (filename[i][0 : fn[i]), raw bytes) -> packed
+ * ingest -> batch scan -> batch encode -> host bytes. DGREP_E_INVALID, with *out
+ * zeroed and before any GPU call: the checks of dgrep_scan_batch; a null
+ * filename or fn array; a null filename[i] with fn[i] != 0; nreduce outside
+ * 1..65535. DGREP_E_UNSUPPORTED (with a message): nsplits * nreduce >= 2^32, or
+ * 2^32 or more matching lines. No DFA loaded: DGREP_E_NO_DFA. A
+ * DGREP_DFA_MATCH_NONE pattern gives total 0 and an all-zero cell_off. */
+int dgrep_map_partitions_batch(dgrep_ctx* ctx, const uint8_t* const* data, const size_t* n,
+                               const char* const* filename, const size_t* fn, size_t nsplits, uint32_t nreduce,
+                               dgrep_batch_partitions* out);
+void dgrep_batch_partitions_free(dgrep_batch_partitions* p);
+
+/* Device form: the records exactly as dgrep_scan_batch_device returned them
+ * over the same packed buffer (line_no and start relative to the record's
+ * split, d_split filled; `count` of them) -> every cell's lines in d_out
+ * (4-byte aligned). Follows dgrep_encode_device's capacity contract: *total =
+ * the bytes needed, nothing is written at or past out_cap; if *total > out_cap
+ * cell_off (host, nsplits * nreduce + 1 entries) is still valid and the caller
+ * calls again with a larger buffer. Records from anywhere else -- a start or
+ * len outside its split, a split id >= nsplits, another order -- are the
+ * caller's responsibility, as with dgrep_encode_device: they are not checked.
+ * DGREP_E_INVALID before any GPU call, with *total = 0: the checks of
+ * dgrep_scan_batch_device (null ctx / total / cell_off / split_len, nsplits,
+ * d_packed, split lengths that do not add up to n_packed), `count` without the
+ * four record arrays, out_cap without d_out, and the filename and nreduce
+ * checks above. DGREP_E_UNSUPPORTED: nsplits * nreduce >= 2^32 or count >=
+ * 2^32. dgrep_last_encode_ms reports the encode's device time. */
+int dgrep_encode_batch_device(dgrep_ctx* ctx, const void* d_packed, size_t n_packed,
+                              const uint64_t* split_len /* host, nsplits */, size_t nsplits,
+                              const uint64_t* d_line_no, const uint64_t* d_start, const uint64_t* d_len,
+                              const uint32_t* d_split, uint64_t count, const char* const* filename, const size_t* fn,
+                              uint32_t nreduce, void* d_out, uint64_t out_cap,
+                              uint64_t* cell_off /* host, nsplits*nreduce+1 */, uint64_t* total);
+
 /* ---- multi-GPU exchange -----------------------------------
  * Replaces the SFTP shipping of map output to the reducers
  * (map_reduce/coordinator.go:136-142) for workers on one node: each worker
