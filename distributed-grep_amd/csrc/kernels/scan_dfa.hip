@@ -2616,7 +2616,12 @@ __global__ __launch_bounds__(256) void order_lines_kernel(const TileInfo* tiles,
                                                           uint64_t ntiles, const uint64_t* bsum_c,
                                                           const uint64_t* bsum_l, uint64_t staging_cap,
                                                           uint64_t capacity, uint64_t* line_no, uint64_t* start,
-                                                          uint64_t* len) {
+                                                          uint64_t* len, const unsigned long long* spec) {
+  // a speculative ordering (queued behind the scan before the host has seen its
+  // counters) stands only if no lane overflowed and no line was parked: the
+  // staged lines change after either, a parked line that does not match would
+  // leave a record past the final count, and the host orders again anyway
+  if (spec && (spec[1] | spec[2])) return;
   const uint64_t waves = uint64_t(gridDim.x) * 4;
   const uint32_t lane = threadIdx.x & 63u;
   for (uint64_t t = uint64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); t < ntiles; t += waves) {
@@ -2905,9 +2910,11 @@ hipError_t scan_dfa_overflow(int kind, const ScanArgs& a, uint64_t nover, hipStr
 }
 
 // out_off / line_base: scratch of ceil(ntiles / 64) entries each (block sums)
+// spec: the scan's counters (overflowing lanes at [1], parked lines at [2]) for a
+// speculative ordering, which does nothing if either is set; else nullptr
 hipError_t order_lines(const TileInfo* tiles, const StagedLine* staging, uint64_t ntiles, uint64_t* out_off,
                        uint64_t* line_base, uint64_t staging_cap, uint64_t capacity, uint64_t* line_no,
-                       uint64_t* start, uint64_t* len, hipStream_t stream) {
+                       uint64_t* start, uint64_t* len, const unsigned long long* spec, hipStream_t stream) {
   // out_off / line_base hold the 64-tile block sums (ceil(ntiles / 64) each)
   const uint64_t nb = (ntiles + 63) / 64;
   const uint64_t bgrid = std::min<uint64_t>((nb + 3) / 4, 4096);
@@ -2915,7 +2922,7 @@ hipError_t order_lines(const TileInfo* tiles, const StagedLine* staging, uint64_
   uint64_t grid = (ntiles + 3) / 4;
   if (grid > 16384) grid = 16384;
   hipLaunchKernelGGL(order_lines_kernel, dim3(grid), dim3(256), 0, stream, tiles, staging, ntiles, out_off,
-                     line_base, staging_cap, capacity, line_no, start, len);
+                     line_base, staging_cap, capacity, line_no, start, len, spec);
   return hipGetLastError();
 }
 

@@ -68,7 +68,7 @@ hipError_t scan_dfa(int kind, const ScanArgs& a, int grid, hipStream_t stream);
 hipError_t scan_dfa_overflow(int kind, const ScanArgs& a, uint64_t nover, hipStream_t stream);
 hipError_t order_lines(const TileInfo* tiles, const StagedLine* staging, uint64_t ntiles, uint64_t* out_off,
                        uint64_t* line_base, uint64_t staging_cap, uint64_t capacity, uint64_t* line_no,
-                       uint64_t* start, uint64_t* len, hipStream_t stream);
+                       uint64_t* start, uint64_t* len, const unsigned long long* spec, hipStream_t stream);
 hipError_t verify_candidates(const VerifyArgs& v, bool candidates, hipStream_t stream);
 hipError_t long_lines_end(const LongArgs& la, hipStream_t stream);
 hipError_t long_lines_resolve(const LongArgs& la, hipStream_t stream);
@@ -1113,9 +1113,12 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     HIPCHK(scan_dfa(launch_kind(c), a, grid, c->stream));
     HIPCHK(hipEventRecord(c->ev1, c->stream));
+    // (the kernel reads the counters itself and leaves the arrays alone if a
+    // lane overflowed or a line was parked: entries [count, capacity) are never
+    // written, and a parked line that does not match would be one)
     if (speculate)
       HIPCHK(order_lines(c->d_tiles, c->d_staging, ntiles, c->d_out_off, c->d_line_base, c->staging_cap, capacity,
-                         d_line, d_start, d_len, c->stream));
+                         d_line, d_start, d_len, c->d_counters, c->stream));
     HIPCHK(hipMemcpyAsync(ctr, c->d_counters, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
     if (DGREP_SYNC_SPIN_US > 0) {
       // block until the scan kernel is done (its wake-up latency overlaps the
@@ -1144,6 +1147,14 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
     } else if (filt && ctr[0] > c->staging_cap) {
       // candidates included, more staged lines than the staging buffer holds
       if ((rc = grow(c, &c->d_staging, &c->staging_cap, ctr[0] + ctr[0] / 8)) != DGREP_OK) return rc;
+    } else if (park && ctr[2] && ctr[0] > c->staging_cap && capacity != 0 && ctr[0] - ctr[2] <= capacity) {
+      // every parked line is staged as one record whether it matches or not: the
+      // staged lines outgrew the staging buffer (sized by `capacity`), but the
+      // matching ones may still fit the caller's arrays once the parked lines
+      // that do not match are dropped -- and only complete staging can be
+      // resolved and ordered. (Ordering the truncated staging here returned a
+      // count <= capacity with wrong records.)
+      if ((rc = grow(c, &c->d_staging, &c->staging_cap, ctr[0])) != DGREP_OK) return rc;
     } else {
       settled = true;
     }
@@ -1224,7 +1235,7 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
     // kept lines are fewer still; a separate wait cost C4 ~30 us a scan)
     if (capacity != 0 && staged <= capacity) {
       HIPCHK(order_lines(c->d_tiles, c->d_staging, ntiles, c->d_out_off, c->d_line_base, c->staging_cap, capacity,
-                         d_line, d_start, d_len, c->stream));
+                         d_line, d_start, d_len, nullptr, c->stream));
       ordered = true;
     }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1271,12 +1282,13 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
   if (filt) c->staged_hint = staged;
   S.matches = total;
   *count = total;
-  // the speculative ordering stands unless the overflow pass, the long-line
-  // resolution or the verification changed the staged lines since
-  const bool order = total != 0 && total <= capacity && (!speculate || over || verify) && !ordered;
+  // the speculative ordering stands (and ran: the kernel tests the same two
+  // counters) unless a lane overflowed or a line was parked
+  const bool spec_stands = speculate && !ctr[1] && !ctr[2];
+  const bool order = total != 0 && total <= capacity && !spec_stands && !ordered;
   if (order)
     HIPCHK(order_lines(c->d_tiles, c->d_staging, ntiles, c->d_out_off, c->d_line_base, c->staging_cap, capacity,
-                       d_line, d_start, d_len, c->stream));
+                       d_line, d_start, d_len, nullptr, c->stream));
   if (over || order) HIPCHK(hipStreamSynchronize(c->stream));
   if (over) {
     HIPCHK(hipEventElapsedTime(&S.overflow_ms, c->ev2, c->ev3));

@@ -212,7 +212,24 @@ void dgrep_reduce_free(dgrep_reduce_out* r);
  * to caller-provided device arrays of `capacity` entries; *count receives
  * the number of matching lines (if > capacity, nothing beyond capacity is
  * written: call again with a larger capacity). Asynchronous on the context
- * stream except for the 8-byte count readback. */
+ * stream except for the 8-byte count readback.
+ *
+ * The capacity contract, on every stepper and pass:
+ * - *count is exact whatever the capacity (0 is a size query), and so is
+ *   dgrep_last_scan_stats' `matches`.
+ * - Entries at index >= capacity are never written.
+ * - *count <= capacity (a full call): entries [0, *count) are the records;
+ *   entries [*count, capacity) are not written.
+ * - *count > capacity (a short call): entries [0, capacity) are unspecified --
+ *   some paths order the first `capacity` records, others write nothing. Call
+ *   again; a short call leaves nothing behind that changes a later call's
+ *   result.
+ * d_data must be 16-byte aligned when n > 0, else DGREP_E_INVALID with nothing
+ * written (a MATCH_NONE pattern returns before the check). With n == 0
+ * d_data is not read and may be unaligned or NULL: the split is the one empty
+ * line, and if the pattern matches it *count = 1 and, given capacity >= 1, the
+ * record is (1, 0, 0). A DGREP_DFA_MATCH_NONE pattern gives *count = 0 and
+ * touches nothing. */
 int dgrep_scan_device(dgrep_ctx* ctx, const void* d_data, size_t n, uint64_t* d_line_no, uint64_t* d_start,
                       uint64_t* d_len, uint64_t capacity, uint64_t* count);
 
@@ -255,7 +272,9 @@ void dgrep_batch_result_free(dgrep_batch_result* r);
 
 /* Device form: the caller packed P itself (n_packed = sum of split_len +
  * nsplits - 1 bytes at d_packed, 16-byte aligned like dgrep_scan_device's
- * split; the other pointers need no alignment beyond their type's). Follows
+ * split -- DGREP_E_INVALID with nothing written otherwise, unless n_packed == 0,
+ * when d_packed is not read and may be unaligned or NULL; the other pointers
+ * need no alignment beyond their type's). Follows
  * dgrep_scan_device's contract: `capacity` entries per result array, *count =
  * the number of matching lines; if *count > capacity nothing is written beyond
  * capacity, d_split_begin is not valid and the caller calls again. d_split_begin
@@ -398,7 +417,8 @@ typedef struct {
                               (shallow DFA states in LDS + candidate verification) */
   uint32_t lane_chunk;     /* bytes per lane chunk */
   uint32_t lane_slots;     /* LDS slots per lane chunk for matching lines */
-  uint32_t scan_attempts;  /* scan launches (2 if the overflow list had to grow) */
+  uint32_t scan_attempts;  /* scan launches: one more for each buffer the scan outgrew (overflow list, pending
+                              list, staging), at most 4 */
   uint64_t tiles;          /* wave tiles of the split */
   uint64_t overflow_lanes; /* lane chunks re-run by the overflow pass */
   uint64_t matches;        /* matching lines */
