@@ -24,6 +24,7 @@
 #include "../kernels/encode.h"
 #include "../kernels/encode_batch.h"
 #include "../kernels/reduce.h"
+#include "../kernels/reduce_batch.h"
 #include "../kernels/scan_common.h"
 #include "../kernels/synth.h"
 #include "pack_pieces.h"
@@ -238,6 +239,13 @@ struct dgrep_ctx {
   uint64_t red_scratch_cap = 0;
   uint8_t* d_red_out = nullptr;
   uint64_t red_out_cap = 0;
+  // every reduce task of a job in one pass (dgrep_reduce_batch* / dgrep_grep_job, kernels/reduce_batch.h)
+  uint64_t* d_rb_seg = nullptr;  // the segment table [nseg + 1] of the forms that take it from the host
+  uint64_t rb_seg_cap = 0;
+  uint64_t* d_rb_off = nullptr;  // part_off [nparts + 1], then lines_in [nparts]
+  uint64_t rb_off_cap = 0;
+  hipEvent_t evr0 = nullptr, evr1 = nullptr;
+  float last_reduce_ms = 0.f;
 };
 
 // the kind handed to the scan entry points: the stepper, with kKindW32 for the
@@ -559,7 +567,8 @@ extern "C" void dgrep_close(dgrep_ctx* c) {
                   c->d_pend, c->d_long_tbl, c->d_st2id, c->d_seg, c->d_seg_off, c->d_segmap, c->d_seg_from, c->d_seg_state, c->d_tiles, c->d_out_off, c->d_line_base, c->d_staging, c->d_counters,
                   c->d_overflow, c->d_data, c->d_res_line, c->d_res_start, c->d_res_len, c->d_enc_scratch,
                   c->d_fname, c->d_bounds, c->d_enc_out, c->d_red_scratch, c->d_red_out, c->d_bat_begin,
-                  c->d_bat_lines, c->d_bat_sums, c->d_res_split, c->d_res_sbegin, c->d_bat_names, c->d_bat_cells};
+                  c->d_bat_lines, c->d_bat_sums, c->d_res_split, c->d_res_sbegin, c->d_bat_names, c->d_bat_cells,
+                  c->d_rb_seg, c->d_rb_off};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
@@ -574,7 +583,7 @@ extern "C" void dgrep_close(dgrep_ctx* c) {
   if (c->ev3) (void)hipEventDestroy(c->ev3);
   if (c->ev4) (void)hipEventDestroy(c->ev4);
   if (c->ev5) (void)hipEventDestroy(c->ev5);
-  for (hipEvent_t e : {c->evb0, c->evb1, c->evb2, c->evb3})
+  for (hipEvent_t e : {c->evb0, c->evb1, c->evb2, c->evb3, c->evr0, c->evr1})
     if (e) (void)hipEventDestroy(e);
   if (c->h_bat_flag) (void)hipHostFree(c->h_bat_flag);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1594,13 +1603,16 @@ static int ingest_ring(dgrep_ctx* c, size_t S, int B) {
 // bytes that fall into it (pack_pieces.h), then DMA'd as in ingest(): the same
 // ring, copy stream and settings. Below 4 MiB, or with chunk 0, the whole of P
 // is assembled in one host staging buffer and copied with one hipMemcpyAsync.
-static int ingest_packed(dgrep_ctx* c, const uint8_t* const* data, const size_t* n, size_t k, size_t total) {
+// `sep` = false lays the inputs back to back with no separator byte (the batch
+// reduce's inputs; `total` is then their plain sum).
+static int ingest_packed(dgrep_ctx* c, const uint8_t* const* data, const size_t* n, size_t k, size_t total,
+                         bool sep = true) {
   const auto t0 = std::chrono::steady_clock::now();
   const int T = std::max(1, c->ingest_threads);
   PackCursor cur;
   std::vector<PackSeg> segs;
   auto fill = [&](uint8_t* dst, size_t len) {
-    pack_piece_segments(n, k, &cur, len, &segs);
+    pack_piece_segments(n, k, &cur, len, &segs, sep);
     for (const PackSeg& s : segs) {
       if (T == 1 || s.split == kPackSeparator || s.len < (size_t(1) << 20)) {
         pack_copy_segment(data, s, dst);
@@ -1878,7 +1890,8 @@ static int build_name_table(dgrep_ctx* c, const char* const* filename, const siz
 }
 
 // Records of a batch scan over P (n bytes at d_packed, k splits, begin[] in
-// c->bat_begin) -> every cell's lines in d_out; cell_off (host, k * nreduce + 1).
+// c->bat_begin) -> every cell's lines in d_out; cell_off (host, k * nreduce + 1;
+// nullptr: the offsets stay on the device in c->d_bat_cells, only the total is read).
 static int encode_batch_resident(dgrep_ctx* c, const uint8_t* d_packed, uint64_t n, uint64_t k, const uint64_t* d_line,
                                  const uint64_t* d_start, const uint64_t* d_len, const uint32_t* d_split,
                                  uint64_t count, const std::vector<uint8_t>& names, uint32_t nreduce, uint8_t* d_out,
@@ -1886,7 +1899,7 @@ static int encode_batch_resident(dgrep_ctx* c, const uint8_t* d_packed, uint64_t
   const uint64_t cells = k * uint64_t(nreduce);
   *total = 0;
   if (count == 0) {
-    memset(cell_off, 0, (cells + 1) * 8);
+    if (cell_off) memset(cell_off, 0, (cells + 1) * 8);
     c->last_encode_ms = 0.f;
     return DGREP_OK;
   }
@@ -1916,10 +1929,11 @@ static int encode_batch_resident(dgrep_ctx* c, const uint8_t* d_packed, uint64_t
   HIPCHK(hipEventRecord(c->ev0, c->stream));
   HIPCHK(encode_batch(a, c->d_enc_scratch, &have, d_out, out_cap, c->d_bat_cells, c->stream));
   HIPCHK(hipEventRecord(c->ev1, c->stream));
-  HIPCHK(hipMemcpyAsync(cell_off, c->d_bat_cells, (cells + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  if (cell_off) HIPCHK(hipMemcpyAsync(cell_off, c->d_bat_cells, (cells + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  else HIPCHK(hipMemcpyAsync(total, c->d_bat_cells + cells, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipEventElapsedTime(&c->last_encode_ms, c->ev0, c->ev1));
-  *total = cell_off[cells];
+  if (cell_off) *total = cell_off[cells];
   return DGREP_OK;
 }
 
@@ -2086,6 +2100,263 @@ extern "C" void dgrep_reduce_free(dgrep_reduce_out* r) {
   if (!r) return;
   free(r->bytes);
   memset(r, 0, sizeof *r);
+}
+
+// ---- every reduce task of a job in one pass (kernels/reduce_batch.h) ---------
+// Core of the batch reduce forms and of the job: data[0:n) is resident at
+// d_data, the segment table (nseg + 1 u64) on the DEVICE at d_seg; nlines = the
+// '\n' in data. One launch train into d_out, then the info words and the
+// partition tables come back with one host wait. part_off (host, nparts + 1),
+// lines_in (host, nparts, may be null); *total = the bytes needed.
+static int reduce_batch_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, const uint64_t* d_seg, uint64_t nseg,
+                                 uint32_t nparts, uint64_t nlines, uint8_t* d_out, uint64_t out_cap,
+                                 uint64_t* part_off, uint64_t* lines_in, uint64_t* total) {
+  *total = 0;
+  if (nlines >= (uint64_t(1) << 32)) {
+    c->err = "batch reduce: 2^32 or more lines";
+    return DGREP_E_UNSUPPORTED;
+  }
+  if (n && (reinterpret_cast<uintptr_t>(d_data) & 15)) {
+    c->err = "batch reduce: the device buffer must be 16-byte aligned";
+    return DGREP_E_INVALID;
+  }
+  int rc;
+  if ((rc = grow(c, &c->d_rb_off, &c->rb_off_cap, 2 * uint64_t(nparts) + 1)) != DGREP_OK) return rc;
+  for (hipEvent_t* e : {&c->evr0, &c->evr1})
+    if (!*e) HIPCHK(hipEventCreate(e));
+  ReduceBatchArgs a;
+  a.data = d_data;
+  a.n = n;
+  a.seg_off = d_seg;
+  a.nseg = nseg;
+  a.nparts = nparts;
+  a.nlines = nlines;
+  uint64_t* d_info = reinterpret_cast<uint64_t*>(c->d_counters);  // 3 of its u64
+  uint64_t* d_part_off = c->d_rb_off;
+  uint64_t* d_lines_in = c->d_rb_off + nparts + 1;
+  size_t need = 0;
+  HIPCHK(reduce_batch(a, nullptr, &need, nullptr, 0, nullptr, nullptr, d_info, c->stream));
+  if ((rc = grow(c, &c->d_red_scratch, &c->red_scratch_cap, need)) != DGREP_OK) return rc;
+  size_t have = c->red_scratch_cap;
+  uint64_t info[3] = {0, 0, 0};
+  HIPCHK(hipEventRecord(c->evr0, c->stream));
+  HIPCHK(reduce_batch(a, c->d_red_scratch, &have, d_out, out_cap, d_part_off, d_lines_in, d_info, c->stream));
+  HIPCHK(hipEventRecord(c->evr1, c->stream));
+  HIPCHK(hipMemcpyAsync(info, d_info, sizeof info, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(part_off, d_part_off, (uint64_t(nparts) + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  if (lines_in) HIPCHK(hipMemcpyAsync(lines_in, d_lines_in, uint64_t(nparts) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipEventElapsedTime(&c->last_reduce_ms, c->evr0, c->evr1));
+  if (info[1] != UINT64_MAX) {
+    memset(part_off, 0, (uint64_t(nparts) + 1) * 8);
+    if (lines_in) memset(lines_in, 0, uint64_t(nparts) * 8);
+    c->err = "reduce input of partition " + std::to_string(reduce_batch_bad_part(info[1])) + ": line " +
+             std::to_string(reduce_batch_bad_line(info[1]) + 1) +
+             ((info[1] & 1) ? " is not a {\"Key\":\"..\",\"Value\":\"..\"} line"
+                            : " is the unfinished last line of a segment (its last byte is not '\\n')");
+    return DGREP_E_INVALID;
+  }
+  if (info[0] != nlines) {
+    c->err = "batch reduce: the line count does not match the buffer";
+    return DGREP_E_INVALID;
+  }
+  *total = info[2];
+  return DGREP_OK;
+}
+
+// the '\n' in d_data[0:n): one kernel and one host wait
+static int reduce_count_host(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64_t* nlines) {
+  uint64_t* d_info = reinterpret_cast<uint64_t*>(c->d_counters);
+  *nlines = 0;
+  if (n == 0) return DGREP_OK;
+  HIPCHK(reduce_count_lines(d_data, n, d_info, c->stream));
+  HIPCHK(hipMemcpyAsync(nlines, d_info, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return DGREP_OK;
+}
+
+// fills a reduce_batch_out from the context's output buffer (after its tables)
+static int reduce_batch_fetch(dgrep_ctx* c, uint64_t total, dgrep_reduce_batch_out* out) {
+  out->total = total;
+  if (total) {
+    out->bytes = static_cast<uint8_t*>(malloc(total));
+    if (!out->bytes) return DGREP_E_NOMEM;
+    HIPCHK(hipMemcpyAsync(out->bytes, c->d_red_out, total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return DGREP_OK;
+}
+
+// the pass into the context's output buffer, grown once if it was too small
+static int reduce_batch_owned(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, const uint64_t* d_seg, uint64_t nseg,
+                              uint32_t nparts, uint64_t nlines, dgrep_reduce_batch_out* out) {
+  int rc;
+  uint64_t total = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if ((rc = reduce_batch_resident(c, d_data, n, d_seg, nseg, nparts, nlines, c->d_red_out, c->red_out_cap,
+                                    out->part_off, out->lines_in, &total)) != DGREP_OK)
+      return rc;
+    if (total <= c->red_out_cap) break;
+    if ((rc = grow(c, &c->d_red_out, &c->red_out_cap, total)) != DGREP_OK) return rc;
+  }
+  return reduce_batch_fetch(c, total, out);
+}
+
+static bool reduce_batch_alloc(dgrep_reduce_batch_out* out, uint32_t nparts) {
+  out->part_off = static_cast<uint64_t*>(calloc(size_t(nparts) + 1, 8));
+  out->lines_in = static_cast<uint64_t*>(calloc(nparts, 8));
+  if (!out->part_off || !out->lines_in) {
+    dgrep_reduce_batch_free(out);
+    return false;
+  }
+  out->nparts = nparts;
+  return true;
+}
+
+extern "C" int dgrep_reduce_batch(dgrep_ctx* c, const uint8_t* const* data, const size_t* n, size_t nparts,
+                                  dgrep_reduce_batch_out* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!c || !out || !data || !n || nparts == 0 || nparts > kReduceBatchMaxParts) return DGREP_E_INVALID;
+  size_t total_in = 0;
+  for (size_t p = 0; p < nparts; ++p) {
+    if (n[p] && !data[p]) return DGREP_E_INVALID;
+    if (n[p] > ~size_t(0) - total_in) {
+      c->err = "dgrep_reduce_batch: the input lengths overflow";
+      return DGREP_E_INVALID;
+    }
+    total_in += n[p];
+  }
+  if (!reduce_batch_alloc(out, uint32_t(nparts))) return DGREP_E_NOMEM;
+  if (total_in == 0) return DGREP_OK;  // nothing to read: every mr-out-<p> is empty
+  auto fail = [&](int rc) {
+    dgrep_reduce_batch_free(out);
+    return rc;
+  };
+  if (hipError_t e = hipSetDevice(c->device); e != hipSuccess) return fail(hip_fail(c, e, "hipSetDevice"));
+  int rc;
+  uint64_t cap = c->data_cap;
+  if ((rc = grow(c, &c->d_data, &cap, (uint64_t(total_in) + 63) & ~uint64_t(63))) != DGREP_OK) return fail(rc);
+  c->data_cap = cap;
+  if ((rc = ingest_packed(c, data, n, nparts, total_in, false)) != DGREP_OK) return fail(rc);
+  std::vector<uint64_t> seg(nparts + 1, 0);
+  for (size_t p = 0; p < nparts; ++p) seg[p + 1] = seg[p] + n[p];
+  if ((rc = grow(c, &c->d_rb_seg, &c->rb_seg_cap, nparts + 1)) != DGREP_OK) return fail(rc);
+  if (hipError_t e = hipMemcpyAsync(c->d_rb_seg, seg.data(), (nparts + 1) * 8, hipMemcpyHostToDevice, c->stream);
+      e != hipSuccess)
+    return fail(hip_fail(c, e, "hipMemcpyAsync"));
+  uint64_t nlines = 0;
+  if ((rc = reduce_count_host(c, c->d_data, total_in, &nlines)) != DGREP_OK) return fail(rc);  // (waits: seg is uploaded)
+  if ((rc = reduce_batch_owned(c, c->d_data, total_in, c->d_rb_seg, nparts, uint32_t(nparts), nlines, out)) != DGREP_OK)
+    return fail(rc);
+  return DGREP_OK;
+}
+
+extern "C" void dgrep_reduce_batch_free(dgrep_reduce_batch_out* r) {
+  if (!r) return;
+  free(r->part_off);
+  free(r->lines_in);
+  free(r->bytes);
+  memset(r, 0, sizeof *r);
+}
+
+extern "C" int dgrep_reduce_batch_device(dgrep_ctx* c, const void* d_data, size_t n, const uint64_t* seg_off,
+                                         size_t nseg, uint32_t nparts, void* d_out, uint64_t out_cap,
+                                         uint64_t* part_off, uint64_t* lines_in, uint64_t* total) {
+  if (total) *total = 0;
+  if (!c || !total || !part_off || !seg_off || nseg == 0 || nparts == 0 || (n && !d_data) || (out_cap && !d_out))
+    return DGREP_E_INVALID;
+  // the limits come before seg_off is read
+  if (nparts > kReduceBatchMaxParts) {
+    c->err = "dgrep_reduce_batch_device: nparts must be at most 65535";
+    return DGREP_E_UNSUPPORTED;
+  }
+  if (uint64_t(nseg) >= (uint64_t(1) << 32)) {
+    c->err = "dgrep_reduce_batch_device: nseg must be below 2^32 segments";
+    return DGREP_E_UNSUPPORTED;
+  }
+  if (nseg % nparts != 0) {
+    c->err = "dgrep_reduce_batch_device: nseg must be a multiple of nparts";
+    return DGREP_E_INVALID;
+  }
+  bool ok = seg_off[0] == 0 && seg_off[nseg] == n;
+  for (size_t g = 0; ok && g < nseg; ++g) ok = seg_off[g] <= seg_off[g + 1];
+  if (!ok) {
+    c->err = "dgrep_reduce_batch_device: seg_off must ascend from 0 to n";
+    return DGREP_E_INVALID;
+  }
+  if (n && (reinterpret_cast<uintptr_t>(d_data) & 15)) {
+    c->err = "dgrep_reduce_batch_device: the device buffer must be 16-byte aligned";
+    return DGREP_E_INVALID;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  int rc;
+  if ((rc = grow(c, &c->d_rb_seg, &c->rb_seg_cap, uint64_t(nseg) + 1)) != DGREP_OK) return rc;
+  HIPCHK(hipMemcpyAsync(c->d_rb_seg, seg_off, (uint64_t(nseg) + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  uint64_t nlines = 0;
+  if ((rc = reduce_count_host(c, static_cast<const uint8_t*>(d_data), n, &nlines)) != DGREP_OK) return rc;
+  return reduce_batch_resident(c, static_cast<const uint8_t*>(d_data), n, c->d_rb_seg, nseg, nparts, nlines,
+                               static_cast<uint8_t*>(d_out), out_cap, part_off, lines_in, total);
+}
+
+// ---- the whole grep job of one worker (worker.go:22-68,161-165 + grep.go) ----
+extern "C" int dgrep_grep_job(dgrep_ctx* c, const uint8_t* const* data, const size_t* n, const char* const* filename,
+                              const size_t* fn, size_t nsplits, uint32_t nreduce, dgrep_reduce_batch_out* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!c || !out || !data || !n || nsplits == 0 || nsplits > UINT32_MAX) return DGREP_E_INVALID;
+  int rc;
+  if ((rc = encode_batch_args(c, filename, fn, nsplits, nreduce)) != DGREP_OK) return rc;
+  for (size_t i = 0; i < nsplits; ++i)
+    if (n[i] && !data[i]) return DGREP_E_INVALID;
+  size_t total_in = 0;
+  if (!pack_total(n, nsplits, &total_in) || total_in == ~size_t(0)) {
+    c->err = "dgrep_grep_job: the split lengths overflow";
+    return DGREP_E_INVALID;
+  }
+  if (uint64_t(nsplits) * nreduce >= (uint64_t(1) << 32)) {
+    c->err = "dgrep_grep_job: nsplits * nreduce must be below 2^32 cells";
+    return DGREP_E_UNSUPPORTED;
+  }
+  if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
+  std::vector<uint8_t> names;
+  if ((rc = build_name_table(c, filename, fn, nsplits, &names)) != DGREP_OK) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  uint64_t count = 0;
+  if ((rc = batch_scan_host(c, data, n, nsplits, total_in, false, &count)) != DGREP_OK) return rc;
+  if (count >= (uint64_t(1) << 32)) { c->err = "more than 2^32-1 records"; return DGREP_E_UNSUPPORTED; }
+  if (!reduce_batch_alloc(out, nreduce)) return DGREP_E_NOMEM;
+  c->last_encode_ms = c->last_reduce_ms = 0.f;
+  if (count == 0) return DGREP_OK;  // no matching line: every mr-out-<r> is empty
+  auto fail = [&](int r) {
+    dgrep_reduce_batch_free(out);
+    return r;
+  };
+  // the cells stay in HBM: the encode's offsets are the reduce's segment table
+  const uint64_t cells = uint64_t(nsplits) * nreduce;
+  uint64_t enc_total = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if ((rc = encode_batch_resident(c, c->d_data, total_in, nsplits, c->d_res_line, c->d_res_start, c->d_res_len,
+                                    c->d_res_split, count, names, nreduce, c->d_enc_out, c->enc_out_cap, nullptr,
+                                    &enc_total)) != DGREP_OK)
+      return fail(rc);
+    if (enc_total <= c->enc_out_cap) break;
+    if ((rc = grow(c, &c->d_enc_out, &c->enc_out_cap, enc_total + enc_total / 16)) != DGREP_OK) return fail(rc);
+  }
+  // one KeyValue line per record; the scratch is sized by the '\n' actually there
+  uint64_t nlines = 0;
+  if ((rc = reduce_count_host(c, c->d_enc_out, enc_total, &nlines)) != DGREP_OK) return fail(rc);
+  if (nlines != count) {
+    c->err = "dgrep_grep_job: the writer's output does not hold one line per record";
+    return fail(DGREP_E_INVALID);
+  }
+  if ((rc = reduce_batch_owned(c, c->d_enc_out, enc_total, c->d_bat_cells, cells, nreduce, nlines, out)) != DGREP_OK)
+    return fail(rc);
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_last_reduce_ms(dgrep_ctx* c, float* ms) {
+  if (!c || !ms) return DGREP_E_INVALID;
+  *ms = c->last_reduce_ms;
+  return DGREP_OK;
 }
 
 extern "C" int dgrep_last_encode_ms(dgrep_ctx* c, float* ms) {

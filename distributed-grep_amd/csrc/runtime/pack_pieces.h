@@ -44,8 +44,11 @@ inline bool pack_total(const size_t* n, size_t k, size_t* total) {
 }
 
 // The segments of the next `len` bytes of P from *cur on (the caller keeps len
-// within what is left of P), in order; *cur moves past them.
-inline void pack_piece_segments(const size_t* n, size_t k, PackCursor* cur, size_t len, std::vector<PackSeg>* segs) {
+// within what is left of P), in order; *cur moves past them. `sep` = false:
+// the splits back to back with no separator byte (P is then their plain
+// concatenation).
+inline void pack_piece_segments(const size_t* n, size_t k, PackCursor* cur, size_t len, std::vector<PackSeg>* segs,
+                                bool sep = true) {
   segs->clear();
   size_t done = 0;
   while (done < len && cur->split < k) {
@@ -56,7 +59,7 @@ inline void pack_piece_segments(const size_t* n, size_t k, PackCursor* cur, size
       cur->off += m;
       done += m;
     } else {
-      if (cur->split + 1 < k) {
+      if (sep && cur->split + 1 < k) {
         segs->push_back(PackSeg{kPackSeparator, 0, done, 1});
         ++done;
       }

@@ -59,6 +59,8 @@ EXPORTS = (
     "dgrep_gather_records", "dgrep_gathered_free", "dgrep_comm_last_error",
     "dgrep_scan_batch", "dgrep_batch_result_free", "dgrep_scan_batch_device", "dgrep_last_batch_ms",
     "dgrep_map_partitions_batch", "dgrep_batch_partitions_free", "dgrep_encode_batch_device",
+    "dgrep_reduce_batch", "dgrep_reduce_batch_free", "dgrep_reduce_batch_device", "dgrep_grep_job",
+    "dgrep_last_reduce_ms",
 )
 COMM_ID_BYTES = 128
 
@@ -115,6 +117,12 @@ class _BatchResult(ctypes.Structure):
 class _BatchPartitions(ctypes.Structure):
     _fields_ = [("nsplits", ctypes.c_uint64), ("nreduce", ctypes.c_uint32), ("total", ctypes.c_uint64),
                 ("cell_off", ctypes.POINTER(ctypes.c_uint64)), ("bytes", ctypes.c_void_p)]
+
+
+class _ReduceBatchOut(ctypes.Structure):
+    _fields_ = [("nparts", ctypes.c_uint32), ("total", ctypes.c_uint64),
+                ("part_off", ctypes.POINTER(ctypes.c_uint64)), ("lines_in", ctypes.POINTER(ctypes.c_uint64)),
+                ("bytes", ctypes.c_void_p)]
 
 
 class _BlobInfo(ctypes.Structure):
@@ -229,6 +237,17 @@ def lib() -> ctypes.CDLL:
             L.dgrep_encode_batch_device.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp, u64, vp, vp, ctypes.c_uint32,
                                                     vp, u64, vp, ctypes.POINTER(u64)]
             L.dgrep_encode_batch_device.restype = i
+            L.dgrep_reduce_batch.argtypes = [vp, vp, vp, sz, ctypes.POINTER(_ReduceBatchOut)]
+            L.dgrep_reduce_batch.restype = i
+            L.dgrep_reduce_batch_free.argtypes = [ctypes.POINTER(_ReduceBatchOut)]
+            L.dgrep_reduce_batch_free.restype = None
+            L.dgrep_reduce_batch_device.argtypes = [vp, vp, sz, vp, sz, ctypes.c_uint32, vp, u64, vp, vp,
+                                                    ctypes.POINTER(u64)]
+            L.dgrep_reduce_batch_device.restype = i
+            L.dgrep_grep_job.argtypes = [vp, vp, vp, vp, vp, sz, ctypes.c_uint32, ctypes.POINTER(_ReduceBatchOut)]
+            L.dgrep_grep_job.restype = i
+            L.dgrep_last_reduce_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+            L.dgrep_last_reduce_ms.restype = i
             _lib = L
     return _lib
 
@@ -519,6 +538,74 @@ class Context:
         finally:
             self._L.dgrep_reduce_free(ctypes.byref(res))
 
+    def _reduce_batch_parts(self, res: "_ReduceBatchOut") -> List[bytes]:
+        try:
+            k = int(res.nparts)
+            raw = ctypes.string_at(res.bytes, res.total) if res.total else b""
+            off = np.ctypeslib.as_array(res.part_off, shape=(k + 1,)).tolist()
+            self.last_lines_in = np.ctypeslib.as_array(res.lines_in, shape=(k,)).tolist()
+            return [raw[off[p]:off[p + 1]] for p in range(k)]
+        finally:
+            self._L.dgrep_reduce_batch_free(ctypes.byref(res))
+
+    def reduce_batch(self, inputs) -> List[bytes]:
+        """Every reduce task of a job in one pass (dgrep_reduce_batch):
+        inputs[p] = the concatenated mr-<map>-<p> files; element p of the result
+        is the content of mr-out-<p>, equal to reduce(inputs[p]). The lines read
+        per partition are left in self.last_lines_in. No input: [] without a C
+        call."""
+        raws = [bytes(x) for x in inputs]
+        if not raws:
+            return []
+        k = len(raws)
+        bufs = [np.frombuffer(r, dtype=np.uint8) for r in raws]  # keep the bytes alive over the call
+        ptrs = (ctypes.c_void_p * k)(*[b.ctypes.data if len(b) else None for b in bufs])
+        lens = (ctypes.c_size_t * k)(*[len(r) for r in raws])
+        res = _ReduceBatchOut()
+        self._check(self._L.dgrep_reduce_batch(self._h, ptrs, lens, k, ctypes.byref(res)))
+        return self._reduce_batch_parts(res)
+
+    def reduce_batch_device(self, d_data: int, n: int, seg_off, nparts: int, d_out: int, out_cap: int):
+        """dgrep_reduce_batch_device over the segments seg_off (host, nseg + 1
+        entries) of the device buffer d_data: returns (part_off list of nparts + 1
+        entries, lines_in list of nparts entries, total)."""
+        seg = np.ascontiguousarray(seg_off, dtype=np.uint64)
+        off = np.zeros(nparts + 1, np.uint64)
+        lin = np.zeros(max(nparts, 1), np.uint64)
+        tot = ctypes.c_uint64()
+        self._check(self._L.dgrep_reduce_batch_device(
+            self._h, ctypes.c_void_p(d_data or None), n, ctypes.c_void_p(seg.ctypes.data if len(seg) else None),
+            max(len(seg), 1) - 1, nparts, ctypes.c_void_p(d_out or None), out_cap, ctypes.c_void_p(off.ctypes.data),
+            ctypes.c_void_p(lin.ctypes.data), ctypes.byref(tot)))
+        return off.tolist(), lin[:nparts].tolist(), int(tot.value)
+
+    def grep_job(self, files, nreduce: int) -> List[bytes]:
+        """The whole grep job of one worker in one call (dgrep_grep_job): files
+        = [(filename, contents), ...] as map_partitions_batch takes them; element
+        r of the result is the content of mr-out-<r>. The intermediate bytes
+        stay on the device. No file: [] without a C call."""
+        files = list(files)
+        if not files:
+            return []
+        as_bytes = lambda x: x.encode("utf-8", "surrogateescape") if isinstance(x, str) else bytes(x)
+        names = [as_bytes(f) for f, _ in files]
+        raws = [as_bytes(c) for _, c in files]
+        k = len(files)
+        bufs = [np.frombuffer(r, dtype=np.uint8) for r in raws]  # keep the bytes alive over the call
+        ptrs = (ctypes.c_void_p * k)(*[b.ctypes.data if len(b) else None for b in bufs])
+        lens = (ctypes.c_size_t * k)(*[len(r) for r in raws])
+        fptrs = (ctypes.c_char_p * k)(*names)
+        flens = (ctypes.c_size_t * k)(*[len(f) for f in names])
+        res = _ReduceBatchOut()
+        self._check(self._L.dgrep_grep_job(self._h, ptrs, lens, fptrs, flens, k, nreduce, ctypes.byref(res)))
+        return self._reduce_batch_parts(res)
+
+    def last_reduce_ms(self) -> float:
+        """Device time of the last batch reduce (dgrep_last_reduce_ms)."""
+        ms = ctypes.c_float()
+        self._check(self._L.dgrep_last_reduce_ms(self._h, ctypes.byref(ms)))
+        return float(ms.value)
+
     def last_encode_ms(self) -> float:
         ms = ctypes.c_float()
         self._check(self._L.dgrep_last_encode_ms(self._h, ctypes.byref(ms)))
@@ -722,6 +809,17 @@ def MapBatch(files: Sequence[Tuple[str, object]]) -> List[List[KeyValue]]:
             kva.append(KeyValue(format_key(filename, ln[r]), v.decode("utf-8", "surrogateescape") if text else v))
         out.append(kva)
     return out
+
+
+def GrepJob(files: Sequence[Tuple[str, object]], nreduce: int) -> List[bytes]:
+    """The whole job for the files a worker holds, with the set pattern
+    (dgrep_grep_job): element r is the content of mr-out-<r>, the "key value\n"
+    lines map_reduce/worker.go:161-165 writes. No file: [] without touching the
+    GPU."""
+    files = list(files)
+    if not files:
+        return []
+    return _context().grep_job(files, nreduce)
 
 
 def Reduce(key: str, values: Sequence[str]) -> str:

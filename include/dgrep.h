@@ -348,6 +348,92 @@ int dgrep_encode_batch_device(dgrep_ctx* ctx, const void* d_packed, size_t n_pac
                               uint32_t nreduce, void* d_out, uint64_t out_cap,
                               uint64_t* cell_off /* host, nsplits*nreduce+1 */, uint64_t* total);
 
+/* ---- every reduce task of a job in one pass; the whole job in one call ------
+ * A job ends at its files mr-out-<r> (map_reduce/worker.go:22-68,161-165, with
+ * the grep plugin's Reduce = values[0], application/grep.go:38-40). The batch
+ * form of dgrep_reduce runs all reduce tasks from one buffer in one launch
+ * train. The buffer is cut into segments by seg_off[nseg + 1] (ascending,
+ * seg_off[0] = 0, the last entry = n; no separator byte between segments);
+ * segment g belongs to partition g % nparts, and partition p's reduce input
+ * is its segments in ascending g, concatenated -- the mr-*-<p> files
+ * readReduceInput reads one after the other. So R separate inputs are nseg =
+ * nparts = R, and the batch writer's cells as they are: nseg = nsplits *
+ * nreduce, nparts = nreduce, seg_off = cell_off. For each partition the result
+ * is exactly the bytes dgrep_reduce returns for that partition's concatenated
+ * input (the same accepted line language, the first line of every distinct
+ * decoded key, in input order); the same key in two partitions is two keys.
+ * Partitions lie in order in `bytes`: mr-out-<p> = bytes[part_off[p] :
+ * part_off[p+1]), part_off[0] = 0, the last entry = total, an empty partition
+ * has equal offsets. Every non-empty segment must end in '\n' (the end of a
+ * file of whole lines): one that does not is malformed input even where its
+ * last line, fused with the next segment's first, would parse. Malformed input
+ * fails the whole call with DGREP_E_INVALID and nothing is returned;
+ * dgrep_last_error names the first malformed line as partition p (0-based)
+ * and line (1-based, within that partition's input) -- the lowest partition,
+ * then the lowest line; a segment without its final '\n' counts as its last
+ * line. */
+typedef struct {
+  uint32_t nparts;
+  uint64_t total;     /* bytes over all partitions */
+  uint64_t* part_off; /* nparts + 1: mr-out-<p> = bytes[part_off[p] : part_off[p+1]) */
+  uint64_t* lines_in; /* nparts: KeyValue lines read for partition p */
+  uint8_t* bytes;
+} dgrep_reduce_batch_out;
+
+/* R = nparts reduce tasks: data[p][0 : n[p]) = the concatenated mr-*-<p> files.
+ * The inputs are ingested back to back through the staging ring and the
+ * dgrep_set_ingest settings (never concatenated on the host above the 4 MiB
+ * direct path). Needs no DFA. DGREP_E_INVALID, with *out zeroed and before any
+ * GPU call: a null ctx, out, data or n; nparts 0 or above 65535; a null
+ * data[p] with n[p] != 0; lengths whose sum overflows. All inputs empty:
+ * DGREP_OK with total 0 and all-zero part_off and lines_in (no GPU call).
+ * DGREP_E_UNSUPPORTED (with a message): 2^32 or more lines. */
+int dgrep_reduce_batch(dgrep_ctx* ctx, const uint8_t* const* data, const size_t* n, size_t nparts,
+                       dgrep_reduce_batch_out* out);
+void dgrep_reduce_batch_free(dgrep_reduce_batch_out* r);
+
+/* Device form: d_data[0 : n) (16-byte aligned when n > 0) and its segment
+ * table -> every partition's bytes in d_out (4-byte aligned). Follows
+ * dgrep_encode_batch_device's capacity contract: *total = the bytes needed,
+ * nothing is written at or past out_cap; part_off (host, nparts + 1) and
+ * lines_in (host, nparts, may be NULL) are valid whenever the input is well
+ * formed, even when *total > out_cap -- the caller then calls again with a
+ * larger buffer. DGREP_E_INVALID before any GPU call, with *total = 0: a null
+ * ctx, total, part_off or seg_off; nseg or nparts 0; nseg not a multiple of
+ * nparts; seg_off[0] != 0, a descending seg_off or seg_off[nseg] != n; n
+ * without d_data; out_cap without d_out; a d_data that is not 16-byte
+ * aligned. DGREP_E_UNSUPPORTED with a message
+ * naming the limit (checked before seg_off is read): nparts above 65535, nseg
+ * >= 2^32; after counting: 2^32 or more lines. dgrep_last_reduce_ms reports the
+ * pass's device time. */
+int dgrep_reduce_batch_device(dgrep_ctx* ctx, const void* d_data, size_t n,
+                              const uint64_t* seg_off /* host, nseg+1 */, size_t nseg, uint32_t nparts, void* d_out,
+                              uint64_t out_cap, uint64_t* part_off /* host, nparts+1 */,
+                              uint64_t* lines_in /* host, nparts, may be NULL */, uint64_t* total);
+
+/* The reference's grep job on one worker's GPU, from the input splits to every
+ * mr-out-<r>: packed ingest -> batch scan -> batch encode into the context's
+ * device buffer -> batch reduce with seg_off = the encode's cell_off, on the
+ * device -> only the outputs are copied back. The intermediate files
+ * mr-<s>-<p> are a transport between workers (worker.go:78-109); within one
+ * worker their bytes never leave HBM. out->nparts = nreduce; out->bytes[
+ * part_off[r] : part_off[r+1]) equals dgrep_reduce over the concatenation of
+ * dgrep_map_partitions_batch's cells (0, r), (1, r), ... Argument checks and
+ * status codes are dgrep_map_partitions_batch's (DGREP_E_NO_DFA, the 2^32-cell
+ * and 2^32-record limits included); a DGREP_DFA_MATCH_NONE pattern, or no
+ * matching line, gives total 0 with all-zero part_off and lines_in.
+ * Afterwards dgrep_last_scan_stats, dgrep_last_encode_ms and
+ * dgrep_last_reduce_ms describe the three legs. The writer's own output
+ * cannot hold a malformed line; should the reduce report one all the same, it
+ * is returned as DGREP_E_INVALID with its message. This call is for a worker
+ * binary that links the library: the Go plugin's Map / Reduce pair cannot
+ * express a whole job. */
+int dgrep_grep_job(dgrep_ctx* ctx, const uint8_t* const* data, const size_t* n, const char* const* filename,
+                   const size_t* fn, size_t nsplits, uint32_t nreduce, dgrep_reduce_batch_out* out);
+
+/* Device time (ms, HIP events on the context stream) of the last batch reduce. */
+int dgrep_last_reduce_ms(dgrep_ctx* ctx, float* ms);
+
 /* ---- multi-GPU exchange -----------------------------------
  * Replaces the SFTP shipping of map output to the reducers
  * (map_reduce/coordinator.go:136-142) for workers on one node: each worker
