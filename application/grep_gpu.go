@@ -31,8 +31,9 @@
 // from C on the GPU (tests/test_abi_c.py).
 //
 // Intended departures from grep.go (fail-stop, never a silent CPU path): a
-// valid Go pattern outside the compiler's subset (DGREP_E_UNSUPPORTED /
-// DGREP_E_TOO_LARGE) panics at the first Map, as does any HIP error; the
+// valid Go pattern outside the compiler's subset (DGREP_E_UNSUPPORTED, or
+// DGREP_E_TOO_LARGE: a DFA over the state budget whose NFA has more than 8192
+// rune-set positions) panics at the first Map, as does any HIP error; the
 // worker dies and the coordinator's 10 s timeout re-assigns the task
 // (map_reduce/coordinator.go:97-124). A pattern Go itself rejects is not a
 // departure: it compiles to a match-nothing blob, as grep.go:21 drops the error.

@@ -1808,9 +1808,12 @@ constexpr uint64_t kVerifyWaveBytes = 16384;
 struct NoWavePred {
   __device__ bool operator()(uint64_t, uint64_t) const { return false; }
 };
-template <class Pred, class WavePred = NoWavePred>
+// kAllWave: every candidate goes to the wave, whatever its length (wide NFA
+// programs, verify_nfa_wave_kernel); line_matches is then never called.
+template <bool kAllWave = false, class Pred, class WavePred = NoWavePred>
 __device__ __forceinline__ void verify_tiles(const VerifyArgs& v, Pred&& line_matches, WavePred&& wave_matches = {}) {
   constexpr bool kWave = !std::is_same<std::decay_t<WavePred>, NoWavePred>::value;
+  static_assert(kWave || !kAllWave, "kAllWave needs a wave predicate");
   const uint32_t lane = threadIdx.x & 63u, wpb = blockDim.x / 64u;
   const uint64_t waves = uint64_t(gridDim.x) * wpb;
   for (uint64_t t = uint64_t(blockIdx.x) * wpb + (threadIdx.x >> 6); t < v.ntiles; t += waves) {
@@ -1833,7 +1836,7 @@ __device__ __forceinline__ void verify_tiles(const VerifyArgs& v, Pred&& line_ma
           L.meta = staged_rel(L) | (uint32_t(P.len >> 32) << kLenHiShift);
         } else if (L.meta & kMetaCand) {
           L.meta &= ~kMetaCand;
-          if (kWave && staged_len(L) > kVerifyWaveBytes)
+          if (kWave && (kAllWave || staged_len(L) > kVerifyWaveBytes))
             wave = true;
           else
             keep = line_matches(L.start, L.start + staged_len(L));
@@ -1929,14 +1932,18 @@ __global__ __launch_bounds__(XR ? 1024 : 256) void verify_kernel(VerifyArgs v) {
 // ---- NFA verification (DGREP_DFA_PARTIAL) -----------------------------------
 // A pattern whose DFA exceeds the compiler's budget ships its first DFA states
 // (the filter) and an NFA program (include/dgrep_blob.h): per rune class, a
-// bit-parallel step over at most 1024 positions (the NFA's rune-set states),
-// with the UTF-8 decoder trie and the context flags (line start, previous rune
-// a word character) the DFA construction uses. One lane per candidate line;
-// the program is small and stays in L2. The position sets live in registers:
-// the kernel is instantiated for up to 256 positions (8 words, the common
-// case) and up to DGREP_NFA_MAX_POS (32 words).
-constexpr uint32_t kNfaMaxWords = DGREP_NFA_MAX_POS / 32;
+// bit-parallel step over the NFA's rune-set states ("positions", at most
+// DGREP_NFA_MAX_POS), with the UTF-8 decoder trie and the context flags (line
+// start, previous rune a word character) the DFA construction uses. Up to 1024
+// positions, one lane per candidate line; the program is small and stays in
+// L2. The position sets live in registers: the kernel is instantiated for up
+// to 256 positions (8 words, the common case) and up to 1024 (kNfaMaxWords =
+// 32 words, the lane-per-line bound). Wider programs take one WAVE per
+// candidate line (verify_nfa_wave_kernel below).
+constexpr uint32_t kNfaMaxWords = 32;
 constexpr uint32_t kNfaSmallWords = 8;
+constexpr uint32_t kNfaWaveMaxSlots = 4;  // position words per lane of the wave kernel
+static_assert(DGREP_NFA_MAX_POS <= 64u * 32u * kNfaWaveMaxSlots, "no kernel for the widest NFA program");
 
 struct NfaView {
   const int32_t* child;
@@ -2019,8 +2026,8 @@ __device__ __forceinline__ void nfa_rune(const NfaView& g, NfaRun<NW>& r, uint32
 
 // one byte through the UTF-8 decoder trie (Go's utf8.DecodeRune: a byte that
 // breaks a sequence flushes its pending bytes as U+FFFD and is decoded afresh)
-template <uint32_t NW>
-__device__ __forceinline__ void nfa_byte(const NfaView& g, NfaRun<NW>& r, uint32_t b) {
+template <class Run>
+__device__ __forceinline__ void nfa_byte(const NfaView& g, Run& r, uint32_t b) {
   int32_t v = g.child[size_t(r.node) * 256 + b];
   if (r.node != 0 && v == -1) {
     for (uint32_t i = 0, d = g.depth[r.node]; i < d && !r.matched; ++i) nfa_rune(g, r, g.fffd);
@@ -2059,6 +2066,104 @@ __device__ __forceinline__ bool nfa_line_matches(const NfaView& g, const uint8_t
   for (uint32_t w = 0; w < NW; ++w)
     if (w < g.nw && (r.P[w] & ex[w])) m = true;
   return m;
+}
+
+// The same program by a whole wave, for position sets too wide for one lane's
+// registers (nw > kNfaMaxWords): word j of P and S lives in lane j & 63, slot
+// j >> 6, so a row (init, has[c], mx, cl[x][ctx], end_x) is one coalesced
+// read of 256 bytes per slot. Words at or beyond nw are 0 and are never read.
+// Every lane walks the same line: begin, pw, node and matched are
+// wave-uniform, and so is all control flow (the ballots see all 64 lanes).
+template <uint32_t SLOTS>
+struct NfaWaveRun {
+  uint32_t P[SLOTS];
+  uint32_t begin, pw, node;
+  bool matched;
+};
+
+// nfa_rune across the wave: the non-zero words of P are found by ballot and
+// broadcast one at a time; for each of their bits every lane ORs its words of
+// cl[x][ctx] into S
+template <uint32_t SLOTS>
+__device__ __forceinline__ void nfa_rune(const NfaView& g, NfaWaveRun<SLOTS>& r, uint32_t c) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t nwf = g.word[c];
+  const uint32_t ctx = g.has_word ? r.pw * 2u + nwf : 0u;
+  const uint32_t nw = g.nw;
+  const uint32_t* ini = g.init + (size_t(r.begin) * g.nctx + ctx) * nw;
+  const uint32_t* mx = g.mx + size_t(ctx) * nw;
+  const bool m = g.init_m[r.begin * g.nctx + ctx] != 0u;
+  uint32_t S[SLOTS];
+  bool hit = false;
+#pragma unroll
+  for (uint32_t k = 0; k < SLOTS; ++k) {
+    const uint32_t j = k * 64u + lane;
+    S[k] = j < nw ? ini[j] : 0u;
+    if (j < nw && (r.P[k] & mx[j])) hit = true;
+  }
+  if (m || __ballot(hit) != 0ull) {
+    r.matched = true;
+    return;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < SLOTS; ++k) {
+    for (uint64_t act = __ballot(r.P[k] != 0u); act; act &= act - 1ull) {
+      const uint32_t src = uint32_t(__ffsll((unsigned long long)act)) - 1u;
+      uint32_t bits = uint32_t(__builtin_amdgcn_readlane(int(r.P[k]), int(src)));
+      // four rows per round, so that their reads are in flight together (a
+      // word with fewer bits left reads its lowest row again: the same OR)
+      while (bits) {
+        const uint32_t x0 = (k * 64u + src) * 32u, lo = uint32_t(__builtin_ctz(bits));
+        const uint32_t* row[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) {
+          const uint32_t x = x0 + (bits ? uint32_t(__builtin_ctz(bits)) : lo);
+          bits &= bits - 1u;
+          row[u] = g.cl + (size_t(x) * g.nctx + ctx) * nw;
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < SLOTS; ++q)
+          if (q * 64u + lane < nw)
+            S[q] |= (row[0][q * 64u + lane] | row[1][q * 64u + lane]) | (row[2][q * 64u + lane] | row[3][q * 64u + lane]);
+      }
+    }
+  }
+  const uint32_t* hc = g.has + size_t(c) * nw;
+#pragma unroll
+  for (uint32_t k = 0; k < SLOTS; ++k) {
+    const uint32_t j = k * 64u + lane;
+    r.P[k] = j < nw ? (S[k] & hc[j]) : 0u;
+  }
+  r.begin = 0;
+  r.pw = g.has_word ? nwf : 0u;
+}
+
+// nfa_line_matches by the wave; (a, e) wave-uniform
+template <uint32_t SLOTS>
+__device__ __forceinline__ bool nfa_wave_line_matches(const NfaView& g, const uint8_t* data, uint64_t a, uint64_t e) {
+  const uint32_t lane = threadIdx.x & 63u;
+  NfaWaveRun<SLOTS> r;
+#pragma unroll
+  for (uint32_t k = 0; k < SLOTS; ++k) r.P[k] = 0;
+  r.begin = 1;
+  r.pw = 0;
+  r.node = 0;
+  r.matched = false;
+  for_line_bytes(data, a, e, [&](uint32_t b) {
+    nfa_byte(g, r, b);
+    return !r.matched;
+  });
+  for (uint32_t i = 0, d = g.depth[r.node]; i < d && !r.matched; ++i) nfa_rune(g, r, g.fffd);
+  if (r.matched) return true;
+  const bool m = g.end_init[r.begin * 2u + r.pw] != 0u;
+  const uint32_t* ex = g.end_x + size_t(r.pw) * g.nw;
+  bool hit = false;
+#pragma unroll
+  for (uint32_t k = 0; k < SLOTS; ++k) {
+    const uint32_t j = k * 64u + lane;
+    if (j < g.nw && (r.P[k] & ex[j])) hit = true;
+  }
+  return m || __ballot(hit) != 0ull;
 }
 
 // The staged lines of a scan with PENDING lines and no filter candidates: only
@@ -2569,6 +2674,23 @@ __global__ __launch_bounds__(256) void verify_nfa_kernel(VerifyArgs v) {
   verify_tiles(v, [&](uint64_t a, uint64_t e) { return nfa_line_matches<NW>(g, v.data, a, e); });
 }
 
+// Programs of more than kNfaMaxWords position words: one wave per candidate
+// line, 64 * SLOTS words (SLOTS = 1, 2, 4) spread over its lanes.
+template <uint32_t SLOTS>
+__global__ __launch_bounds__(256) void verify_nfa_wave_kernel(VerifyArgs v) {
+  const NfaView g = nfa_view(v.nfa);
+  verify_tiles<true>(
+      v, [](uint64_t, uint64_t) { return false; },
+      [&](uint64_t a, uint64_t e) {
+        // the same in every lane (verify_tiles broadcasts them): as scalars
+        const uint64_t ua = (uint64_t(__builtin_amdgcn_readfirstlane(uint32_t(a >> 32))) << 32) |
+                            uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(a)));
+        const uint64_t ue = (uint64_t(__builtin_amdgcn_readfirstlane(uint32_t(e >> 32))) << 32) |
+                            uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(e)));
+        return nfa_wave_line_matches<SLOTS>(g, v.data, ua, ue);
+      });
+}
+
 // ---- ordering passes ------------------------------------------------------
 // Tiles append their lines to the staging buffer in atomic order; these passes
 // place every tile's lines at its final output index (exclusive prefix of the
@@ -2989,8 +3111,16 @@ hipError_t verify_candidates(const VerifyArgs& v, bool candidates, hipStream_t s
     hipLaunchKernelGGL(resolve_tiles_kernel, dim3(grid), dim3(256), 0, stream, v);
   else if (v.nfa && v.nfa_words <= kNfaSmallWords)
     hipLaunchKernelGGL(verify_nfa_kernel<kNfaSmallWords>, dim3(grid), dim3(256), 0, stream, v);
-  else if (v.nfa)
+  else if (v.nfa && v.nfa_words <= kNfaMaxWords)
     hipLaunchKernelGGL(verify_nfa_kernel<kNfaMaxWords>, dim3(grid), dim3(256), 0, stream, v);
+  else if (v.nfa && v.nfa_words <= 64)
+    hipLaunchKernelGGL(verify_nfa_wave_kernel<1>, dim3(grid), dim3(256), 0, stream, v);
+  else if (v.nfa && v.nfa_words <= 128)
+    hipLaunchKernelGGL(verify_nfa_wave_kernel<2>, dim3(grid), dim3(256), 0, stream, v);
+  else if (v.nfa && v.nfa_words <= 64 * kNfaWaveMaxSlots)
+    hipLaunchKernelGGL(verify_nfa_wave_kernel<kNfaWaveMaxSlots>, dim3(grid), dim3(256), 0, stream, v);
+  else if (v.nfa)
+    return hipErrorInvalidValue;  // wider than any kernel: the loader refuses such a program
   else if (v.full_u32)
     hipLaunchKernelGGL((verify_kernel<uint32_t, false>), dim3(grid), dim3(256), 0, stream, v);
   else if (v.ximg)

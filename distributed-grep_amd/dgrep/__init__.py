@@ -297,6 +297,16 @@ class CompiledPattern:
         return np.frombuffer(self.blob[288 + 4 * ne:], dtype=np.uint32)
 
     @property
+    def nfa_positions(self) -> int:
+        """Rune-set positions (npos) of a partial blob's NFA program, 0 for any
+        other blob. Up to 1024 a candidate line is decided by one lane, above
+        that (up to 8192, DGREP_NFA_MAX_POS) by one wave."""
+        if not self.partial:
+            return 0
+        at = 288 + 4 * self.nstates * self.nclasses + 4  # the program's second word
+        return int.from_bytes(self.blob[at:at + 4], "little")
+
+    @property
     def go_syntax_error(self) -> bool:
         return bool(self.flags & DFA_GO_SYNTAX_ERROR)
 

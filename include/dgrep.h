@@ -40,7 +40,7 @@ enum {
   DGREP_OK = 0,
   DGREP_E_INVALID = 1,     /* bad argument / malformed blob */
   DGREP_E_UNSUPPORTED = 2, /* valid Go regexp outside the compiler's subset: refuse, never guess */
-  DGREP_E_TOO_LARGE = 3,   /* automaton exceeds the compiler's state budget */
+  DGREP_E_TOO_LARGE = 3,   /* DFA over the state budget AND its NFA over DGREP_NFA_MAX_POS (8192) positions */
   DGREP_E_HIP = 4,         /* HIP runtime error (message in dgrep_last_error) */
   DGREP_E_NOMEM = 5,
   DGREP_E_NO_DFA = 6,      /* scan before dgrep_load_dfa */

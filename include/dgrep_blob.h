@@ -66,8 +66,12 @@ typedef struct {
  * if init_m[begin][ctx] or P & mx[ctx] != 0; else P = S & has[c], begin = 0,
  * prev_word = word[c]. At the end of the line (pending decoder bytes flushed as
  * U+FFFD runes) it matches if end_init[begin][prev_word] or P & end_x[prev_word].
+ *
+ * DGREP_NFA_MAX_POS bounds npos (nw <= 256, so the dense cl table is at most
+ * 8 MiB per context); a pattern over the state budget whose NFA has more
+ * positions is refused with DGREP_E_TOO_LARGE.
  */
 #define DGREP_NFA_MAGIC 0x3141464eu /* "NFA1" */
-#define DGREP_NFA_MAX_POS 1024u
+#define DGREP_NFA_MAX_POS 8192u
 
 #endif
