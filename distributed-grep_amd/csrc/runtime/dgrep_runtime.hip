@@ -27,6 +27,7 @@
 #include "../kernels/reduce_batch.h"
 #include "../kernels/scan_common.h"
 #include "../kernels/synth.h"
+#include "../kernels/window.h"
 #include "pack_pieces.h"
 
 // DFAs of at most this many states use the Sheng stepper (8 = its limit; 0
@@ -102,6 +103,7 @@ struct dgrep_ctx {
 
   // loaded pattern
   bool loaded = false;
+  uint64_t load_gen = 0;  // dgrep_load_dfa calls: a stream opened under another pattern is refused (dgrep_stream_*)
   uint32_t flags = 0, nstates = 0, start = 0, start_m = 0;
   bool empty_line_matches = false;
   uint8_t* d_table = nullptr;  // stepper image (see dgrep_load_dfa)
@@ -683,6 +685,7 @@ extern "C" int dgrep_load_dfa(dgrep_ctx* c, const void* blob, size_t n) {
     start_m = f_m;
   }
   c->loaded = false;  // the previous pattern's verification tables go now
+  ++c->load_gen;
   if (c->d_nfa) HIPCHK(hipFree(c->d_nfa));
   c->d_nfa = nullptr;
   if (c->d_full) HIPCHK(hipFree(c->d_full));
@@ -1748,6 +1751,539 @@ extern "C" int dgrep_last_batch_ms(dgrep_ctx* c, float* newline_ms, float* rebas
   if (!c || !newline_ms || !rebase_ms) return DGREP_E_INVALID;
   *newline_ms = c->last_newline_ms;
   *rebase_ms = c->last_rebase_ms;
+  return DGREP_OK;
+}
+
+// ---- a split consumed in windows (kernels/window.h) --------------------------
+// One map task per input file (map_reduce/worker.go:72-76) makes a split "one
+// unbounded string per file". The windowed forms keep only two window buffers
+// on the device: while the scan runs on one, the next piece is DMA'd into the
+// other, behind the carried tail. Each window's completed lines are scanned by
+// scan_resident as they are and their records rebased by the stream's running
+// (byte_base, line_base), so the concatenated records are those of dgrep_scan
+// on the concatenated bytes, for every cut.
+struct dgrep_stream {
+  dgrep_ctx* c = nullptr;
+  size_t window = 0;
+  uint32_t flags = 0;
+  uint64_t gen = 0;        // the context's load generation at open
+  int status = DGREP_OK;   // a HIP error or out-of-memory mid-stream: every later call returns it
+  bool finished = false;
+  // the two window buffers; buf[cur][0 : fill) is the carried tail
+  uint8_t* buf[2] = {nullptr, nullptr};
+  uint64_t cap[2] = {0, 0};
+  int cur = 0;
+  uint64_t fill = 0;
+  uint64_t byte_base = 0, line_base = 0;
+  // device: the cut pass's partials [3 kCutBlocks], its result [3], the gather's total [1]; pinned: the last four
+  unsigned long long* d_cut = nullptr;
+  unsigned long long* h_cut = nullptr;
+  hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;   // the cut pass
+  hipEvent_t ev_free[2] = {nullptr, nullptr};    // buffer b's last reader on the context stream
+  hipEvent_t ev_in = nullptr;                    // the last copy into buf[cur] on the copy stream
+  // the call's records so far (device), and its values (host)
+  uint64_t* d_line = nullptr;
+  uint64_t* d_start = nullptr;
+  uint64_t* d_len = nullptr;
+  uint64_t* d_voff = nullptr;  // [acc_cap + 1], DGREP_STREAM_VALUES
+  uint64_t acc_cap = 0, nrec = 0;
+  uint8_t* d_values = nullptr;  // one window's gathered lines
+  uint64_t values_cap = 0;
+  uint8_t* d_gscratch = nullptr;
+  uint64_t gscratch_cap = 0;
+  uint8_t* h_values = nullptr;
+  uint64_t h_values_cap = 0, vbytes = 0;
+  // dgrep_stream_stats
+  uint64_t windows = 0, max_carry = 0;
+  float cut_ms = 0.f;
+  // the call's scan stats, summed over its windows
+  dgrep_scan_stats agg{};
+  float agg_ms = 0.f;
+};
+
+static uint32_t sat_add32(uint32_t a, uint32_t b) { return uint32_t(std::min<uint64_t>(uint64_t(a) + b, UINT32_MAX)); }
+
+static void win_stats_begin(dgrep_stream* s) {
+  s->agg = dgrep_scan_stats{};
+  s->agg.stepper = uint32_t(s->c->step_kind);
+  s->agg_ms = 0.f;
+}
+
+// one window's scan (the context's stats) added to the call's
+static void win_stats_add(dgrep_stream* s, uint64_t n) {
+  const dgrep_scan_stats& w = s->c->stats;
+  dgrep_scan_stats& a = s->agg;
+  if (n) {
+    a.stepper = w.stepper;
+    a.lane_chunk = w.lane_chunk;
+    a.lane_slots = w.lane_slots;
+  }
+  a.scan_attempts = sat_add32(a.scan_attempts, w.scan_attempts);
+  a.long_guess_misses = sat_add32(a.long_guess_misses, w.long_guess_misses);
+  a.long_segments = sat_add32(a.long_segments, w.long_segments);
+  a.tiles += w.tiles;
+  a.overflow_lanes += w.overflow_lanes;
+  a.matches += w.matches;
+  a.candidates += w.candidates;
+  a.pending += w.pending;
+  a.scan_ms += w.scan_ms;
+  a.overflow_ms += w.overflow_ms;
+  a.verify_ms += w.verify_ms;
+  s->agg_ms += s->c->last_ms;
+}
+
+static void win_stats_end(dgrep_stream* s) {
+  s->c->stats = s->agg;
+  s->c->last_ms = s->agg_ms;
+}
+
+// buf[b] holds at least `need` bytes (and the padding the kernels' aligned
+// reads may touch); its first `keep` bytes survive a reallocation.
+static int win_reserve(dgrep_stream* s, int b, uint64_t need, uint64_t keep) {
+  dgrep_ctx* c = s->c;
+  const uint64_t want = ((need + 255) & ~uint64_t(255)) + 64;
+  if (s->buf[b] && s->cap[b] >= want) return DGREP_OK;
+  uint8_t* p = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&p), want) != hipSuccess) {
+    (void)hipGetLastError();
+    c->err = "window buffer: out of device memory (" + std::to_string(want) + " bytes)";
+    return DGREP_E_NOMEM;
+  }
+  if (s->buf[b]) {
+    // copies into the old buffer (the carried tail) are in order on the copy stream
+    HIPCHK(hipStreamSynchronize(c->copy_stream));
+    if (keep) HIPCHK(hipMemcpyAsync(p, s->buf[b], keep, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipFree(s->buf[b]));
+  }
+  s->buf[b] = p;
+  s->cap[b] = want;
+  return DGREP_OK;
+}
+
+// Host bytes -> dst on the copy stream, through the staging ring and the
+// dgrep_set_ingest settings as ingest() does; below the 4 MiB direct-path
+// threshold, or with chunk 0, one pageable copy. The ring may still hold the
+// window before: a staging buffer is refilled once its last DMA is done.
+// Returns with the last copy queued and s->ev_in recorded behind it.
+static int win_ingest(dgrep_stream* s, uint8_t* dst, const uint8_t* src, size_t len) {
+  dgrep_ctx* c = s->c;
+  if (c->ingest_chunk == 0 || len < (size_t(4) << 20)) {
+    HIPCHK(hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, c->copy_stream));
+    HIPCHK(hipEventRecord(s->ev_in, c->copy_stream));
+    return DGREP_OK;
+  }
+  const size_t S = c->ingest_chunk;
+  const int B = std::max(2, c->ingest_bufs), T = std::max(1, c->ingest_threads);
+  int rc;
+  if ((rc = ingest_ring(c, S, B)) != DGREP_OK) return rc;
+  const size_t pieces = (len + S - 1) / S;
+  for (size_t k = 0; k < pieces; ++k) {
+    const int b = int(k % size_t(B));
+    const size_t off = k * S, m = std::min(S, len - off);
+    HIPCHK(hipEventSynchronize(c->ev_stage[b]));  // buffer b's last DMA is done (or it never had one)
+    uint8_t* h = c->h_stage[b];
+    const uint8_t* from = src + off;
+    if (T == 1 || m < (size_t(1) << 20)) {
+      memcpy(h, from, m);
+    } else {
+      std::vector<std::thread> th;
+      const size_t part = ((m + T - 1) / T + 4095) & ~size_t(4095);
+      for (int t = 0; t < T; ++t) {
+        const size_t a = size_t(t) * part;
+        if (a >= m) break;
+        const size_t q = std::min(part, m - a);
+        th.emplace_back([=] { memcpy(h + a, from + a, q); });
+      }
+      for (auto& x : th) x.join();
+    }
+    HIPCHK(hipMemcpyAsync(dst + off, h, m, hipMemcpyHostToDevice, c->copy_stream));
+    HIPCHK(hipEventRecord(c->ev_stage[b], c->copy_stream));
+  }
+  HIPCHK(hipEventRecord(s->ev_in, c->copy_stream));
+  return DGREP_OK;
+}
+
+// the call's record arrays hold `need` records; the nrec there survive
+static int win_acc_reserve(dgrep_stream* s, uint64_t need) {
+  dgrep_ctx* c = s->c;
+  if (need <= s->acc_cap) return DGREP_OK;
+  const uint64_t cap = std::max<uint64_t>(need, std::max<uint64_t>(1024, 2 * s->acc_cap));
+  const bool values = (s->flags & DGREP_STREAM_VALUES) != 0;
+  uint64_t* fresh[4] = {nullptr, nullptr, nullptr, nullptr};
+  uint64_t** old[4] = {&s->d_line, &s->d_start, &s->d_len, &s->d_voff};
+  for (int i = 0; i < (values ? 4 : 3); ++i) {
+    const uint64_t extra = i == 3 ? 1 : 0;
+    if (hipMalloc(reinterpret_cast<void**>(&fresh[i]), (cap + extra) * 8) != hipSuccess) {
+      (void)hipGetLastError();
+      for (uint64_t* f : fresh)
+        if (f) (void)hipFree(f);
+      c->err = "windowed scan: out of device memory for " + std::to_string(cap) + " records";
+      return DGREP_E_NOMEM;
+    }
+    if (*old[i] && s->nrec)
+      HIPCHK(hipMemcpyAsync(fresh[i], *old[i], (s->nrec + extra) * 8, hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < 4; ++i) {
+    if (*old[i]) HIPCHK(hipFree(*old[i]));
+    *old[i] = fresh[i];
+  }
+  s->acc_cap = cap;
+  return DGREP_OK;
+}
+
+// One window's completed lines d[0 : n) (16-byte aligned; n may be 0, the one
+// empty line): scan, then the records rebased and appended to the call's, then
+// their bytes gathered.
+static int win_scan(dgrep_stream* s, const uint8_t* d, uint64_t n) {
+  dgrep_ctx* c = s->c;
+  int rc;
+  uint64_t count = 0;
+  uint64_t want = std::max<uint64_t>(c->res_cap, std::max<uint64_t>(1024, n / 512));
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if ((rc = grow_results(c, want)) != DGREP_OK) return rc;
+    if ((rc = scan_resident(c, d, n, c->d_res_line, c->d_res_start, c->d_res_len, c->res_cap, &count)) != DGREP_OK)
+      return rc;
+    if (count <= c->res_cap) break;
+    want = count;
+  }
+  win_stats_add(s, n);
+  ++s->windows;
+  if (count == 0) return DGREP_OK;
+  if ((rc = win_acc_reserve(s, s->nrec + count)) != DGREP_OK) return rc;
+  HIPCHK(window_rebase_append(c->d_res_line, c->d_res_start, c->d_res_len, count, s->line_base, s->byte_base,
+                              s->d_line + s->nrec, s->d_start + s->nrec, s->d_len + s->nrec, c->num_cus, c->stream));
+  if (s->flags & DGREP_STREAM_VALUES) {
+    if (count >= (uint64_t(1) << 31)) {
+      c->err = "windowed scan: 2^31 or more matching lines in one window";
+      return DGREP_E_UNSUPPORTED;
+    }
+    // the lines lie apart in the region: their bytes sum to at most n
+    if ((rc = grow(c, &s->d_values, &s->values_cap, std::max<uint64_t>(n, 1))) != DGREP_OK) return rc;
+    GatherArgs g;
+    g.data = d;
+    g.start = c->d_res_start;
+    g.len = c->d_res_len;
+    g.nrec = count;
+    g.value_base = s->vbytes;
+    g.value_off = s->d_voff + s->nrec;
+    g.values = s->d_values;
+    g.total = s->d_cut + 3 * kCutBlocks + 3;
+    size_t need = 0;
+    HIPCHK(window_gather(g, nullptr, &need, c->num_cus, c->stream));
+    if ((rc = grow(c, &s->d_gscratch, &s->gscratch_cap, need)) != DGREP_OK) return rc;
+    size_t have = s->gscratch_cap;
+    HIPCHK(window_gather(g, s->d_gscratch, &have, c->num_cus, c->stream));
+    HIPCHK(hipMemcpyAsync(s->h_cut + 3, g.total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint64_t wt = s->h_cut[3];
+    if (wt > n) {
+      c->err = "windowed scan: gathered more bytes than the window holds";
+      return DGREP_E_HIP;
+    }
+    if (s->vbytes + wt > s->h_values_cap) {
+      const uint64_t cap = std::max<uint64_t>(s->vbytes + wt, 2 * s->h_values_cap);
+      uint8_t* p = static_cast<uint8_t*>(realloc(s->h_values, cap));
+      if (!p) return DGREP_E_NOMEM;
+      s->h_values = p;
+      s->h_values_cap = cap;
+    }
+    if (wt) {
+      HIPCHK(hipMemcpyAsync(s->h_values + s->vbytes, s->d_values, wt, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    s->vbytes += wt;
+  }
+  s->nrec += count;
+  return DGREP_OK;
+}
+
+// The feed's bytes, in pieces of at most one window. Every piece is a window
+// that is not the last: the cut pass finds the last '\n' of the carried tail
+// plus the piece, the tail behind it is carried to the other buffer and the
+// next piece's DMA queued behind the tail -- both before the host waits for
+// this window's scan. Returns with every copy out of `data` done.
+static int win_feed(dgrep_stream* s, const uint8_t* data, size_t n) {
+  dgrep_ctx* c = s->c;
+  int rc;
+  size_t off = 0;
+  uint64_t pending = std::min<uint64_t>(s->window, n);  // bytes queued behind the tail in buf[cur]
+  if (pending) {
+    if ((rc = win_reserve(s, s->cur, s->fill + pending, s->fill)) != DGREP_OK) return rc;
+    if ((rc = win_ingest(s, s->buf[s->cur] + s->fill, data, pending)) != DGREP_OK) return rc;
+    off = pending;
+  }
+  unsigned long long* const d_res = s->d_cut + 3 * kCutBlocks;
+  while (pending) {
+    const uint64_t F = s->fill + pending;
+    HIPCHK(hipStreamWaitEvent(c->stream, s->ev_in, 0));
+    HIPCHK(hipEventRecord(s->ev_c0, c->stream));
+    HIPCHK(window_cut(s->buf[s->cur], F, s->fill, s->d_cut, d_res, c->num_cus, c->stream));
+    HIPCHK(hipEventRecord(s->ev_c1, c->stream));
+    HIPCHK(hipMemcpyAsync(s->h_cut, d_res, 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, s->ev_c0, s->ev_c1));
+    s->cut_ms += ms;
+    const uint64_t last1 = s->h_cut[0], nl = s->h_cut[1];
+    if (last1 > F) {
+      c->err = "windowed scan: the cut lies past the window";
+      return DGREP_E_HIP;
+    }
+    const uint64_t next = std::min<uint64_t>(s->window, n - off);
+    if (last1 == 0) {
+      // no line completed: all of it is the tail, and the next piece lands behind it
+      s->fill = F;
+      s->max_carry = std::max(s->max_carry, F);
+      pending = next;
+      if (next) {
+        if ((rc = win_reserve(s, s->cur, F + next, F)) != DGREP_OK) return rc;
+        if ((rc = win_ingest(s, s->buf[s->cur] + F, data + off, next)) != DGREP_OK) return rc;
+        off += next;
+      }
+      continue;
+    }
+    const uint64_t cut = last1 - 1, tail = F - last1;
+    // the line the carried tail began ends at the first '\n' behind the tail: its whole length was held
+    if (s->fill && s->h_cut[2]) s->max_carry = std::max<uint64_t>(s->max_carry, s->h_cut[2] - 1);
+    const int o = s->cur ^ 1;
+    if ((rc = win_reserve(s, o, tail + next, 0)) != DGREP_OK) return rc;
+    HIPCHK(hipStreamWaitEvent(c->copy_stream, s->ev_free[o], 0));
+    if (tail)
+      HIPCHK(hipMemcpyAsync(s->buf[o], s->buf[s->cur] + last1, tail, hipMemcpyDeviceToDevice, c->copy_stream));
+    if (next) {
+      if ((rc = win_ingest(s, s->buf[o] + tail, data + off, next)) != DGREP_OK) return rc;
+      off += next;
+    } else {
+      HIPCHK(hipEventRecord(s->ev_in, c->copy_stream));
+    }
+    if ((rc = win_scan(s, s->buf[s->cur], cut)) != DGREP_OK) return rc;
+    HIPCHK(hipEventRecord(s->ev_free[s->cur], c->stream));
+    s->byte_base += last1;
+    s->line_base += nl;
+    s->cur = o;
+    s->fill = tail;
+    s->max_carry = std::max(s->max_carry, tail);
+    pending = next;
+  }
+  return DGREP_OK;
+}
+
+// the end of the stream: what is left is its last line (maybe the empty one)
+static int win_finish(dgrep_stream* s) {
+  dgrep_ctx* c = s->c;
+  HIPCHK(hipStreamWaitEvent(c->stream, s->ev_in, 0));
+  const int rc = win_scan(s, s->buf[s->cur], s->fill);
+  if (rc == DGREP_OK) s->finished = true;
+  return rc;
+}
+
+// The call's records (and values) to the host, malloc'd; the stream starts its
+// next call's result empty.
+static int win_collect(dgrep_stream* s, dgrep_stream_result* out) {
+  dgrep_ctx* c = s->c;
+  const uint64_t count = s->nrec;
+  const bool values = (s->flags & DGREP_STREAM_VALUES) != 0;
+  out->count = count;
+  if (count) {
+    out->line_no = static_cast<uint64_t*>(malloc(count * 8));
+    out->start = static_cast<uint64_t*>(malloc(count * 8));
+    out->len = static_cast<uint64_t*>(malloc(count * 8));
+  }
+  if (values) out->value_off = static_cast<uint64_t*>(malloc((count + 1) * 8));
+  if ((count && (!out->line_no || !out->start || !out->len)) || (values && !out->value_off)) {
+    dgrep_stream_result_free(out);
+    return DGREP_E_NOMEM;
+  }
+  if (count) {
+    HIPCHK(hipMemcpyAsync(out->line_no, s->d_line, count * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out->start, s->d_start, count * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out->len, s->d_len, count * 8, hipMemcpyDeviceToHost, c->stream));
+    if (values)
+      HIPCHK(hipMemcpyAsync(out->value_off + 1, s->d_voff + 1, count * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  if (values) {
+    out->value_off[0] = 0;
+    out->values = s->h_values;
+    s->h_values = nullptr;
+    s->h_values_cap = 0;
+  }
+  s->nrec = 0;
+  s->vbytes = 0;
+  return DGREP_OK;
+}
+
+static bool win_window_ok(size_t window_bytes) {
+  return window_bytes >= 4096 && window_bytes <= (size_t(1) << 40) && window_bytes % 4096 == 0;
+}
+
+static int win_open(dgrep_ctx* c, size_t window_bytes, uint32_t flags, dgrep_stream** out) {
+  dgrep_stream* s = new dgrep_stream();
+  s->c = c;
+  s->window = window_bytes;
+  s->flags = flags;
+  s->gen = c->load_gen;
+  *out = s;  // kept on failure too: dgrep_stream_close frees what was made
+  if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->d_cut), (3 * kCutBlocks + 4) * sizeof(unsigned long long)));
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_cut), 4 * sizeof(unsigned long long), hipHostMallocDefault));
+  HIPCHK(hipEventCreate(&s->ev_c0));
+  HIPCHK(hipEventCreate(&s->ev_c1));
+  for (hipEvent_t* e : {&s->ev_free[0], &s->ev_free[1], &s->ev_in})
+    HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  return DGREP_OK;
+}
+
+extern "C" void dgrep_stream_close(dgrep_stream* s) {
+  if (!s) return;
+  dgrep_ctx* c = s->c;
+  (void)hipSetDevice(c->device);
+  if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  void* bufs[] = {s->buf[0], s->buf[1], s->d_cut, s->d_line, s->d_start, s->d_len, s->d_voff, s->d_values, s->d_gscratch};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+  if (s->h_cut) (void)hipHostFree(s->h_cut);
+  for (hipEvent_t e : {s->ev_c0, s->ev_c1, s->ev_free[0], s->ev_free[1], s->ev_in})
+    if (e) (void)hipEventDestroy(e);
+  free(s->h_values);
+  delete s;
+}
+
+extern "C" void dgrep_stream_result_free(dgrep_stream_result* r) {
+  if (!r) return;
+  free(r->line_no);
+  free(r->start);
+  free(r->len);
+  free(r->value_off);
+  free(r->values);
+  memset(r, 0, sizeof *r);
+}
+
+extern "C" int dgrep_stream_open(dgrep_ctx* c, size_t window_bytes, uint32_t flags, dgrep_stream** out) {
+  if (out) *out = nullptr;
+  if (!c || !out || (flags & ~uint32_t(DGREP_STREAM_VALUES))) return DGREP_E_INVALID;
+  if (!win_window_ok(window_bytes)) {
+    c->err = "window_bytes must be a multiple of 4096 in [4096, 2^40]";
+    return DGREP_E_INVALID;
+  }
+  if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
+  HIPCHK(hipSetDevice(c->device));
+  const int rc = win_open(c, window_bytes, flags, out);
+  if (rc != DGREP_OK) {
+    dgrep_stream_close(*out);
+    *out = nullptr;
+  }
+  return rc;
+}
+
+// The checks every stream call makes before it touches the GPU.
+static int win_enter(dgrep_stream* s, bool feeding) {
+  dgrep_ctx* c = s->c;
+  if (s->status != DGREP_OK) return s->status;
+  if (s->finished) {
+    c->err = feeding ? "dgrep_stream_feed after dgrep_stream_finish" : "dgrep_stream_finish called twice";
+    return DGREP_E_INVALID;
+  }
+  if (s->gen != c->load_gen) {
+    c->err = "a pattern was loaded while this stream was open: its records would mix two patterns";
+    return DGREP_E_INVALID;
+  }
+  return DGREP_OK;
+}
+
+// a failure mid-stream leaves the stream unusable; nothing of the caller's is read after the return
+static int win_fail(dgrep_stream* s, int rc) {
+  if (rc == DGREP_OK) return rc;
+  dgrep_ctx* c = s->c;
+  const std::string msg = c->err;
+  s->status = rc;
+  if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  (void)hipGetLastError();
+  c->err = msg;
+  return rc;
+}
+
+extern "C" int dgrep_stream_feed(dgrep_stream* s, const uint8_t* data, size_t n, dgrep_stream_result* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!s || !out || (n && !data)) return DGREP_E_INVALID;
+  dgrep_ctx* c = s->c;
+  int rc;
+  if ((rc = win_enter(s, true)) != DGREP_OK) return rc;
+  win_stats_begin(s);
+  if (n && !(c->flags & DGREP_DFA_MATCH_NONE)) {
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = win_fail(s, win_feed(s, data, n))) != DGREP_OK) return rc;
+    if ((rc = win_fail(s, win_collect(s, out))) != DGREP_OK) return rc;
+  } else if (s->flags & DGREP_STREAM_VALUES) {
+    if (!(out->value_off = static_cast<uint64_t*>(calloc(1, 8)))) return DGREP_E_NOMEM;
+  }
+  win_stats_end(s);
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_stream_finish(dgrep_stream* s, dgrep_stream_result* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!s || !out) return DGREP_E_INVALID;
+  dgrep_ctx* c = s->c;
+  int rc;
+  if ((rc = win_enter(s, false)) != DGREP_OK) return rc;
+  win_stats_begin(s);
+  if (!(c->flags & DGREP_DFA_MATCH_NONE)) {
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = win_fail(s, win_finish(s))) != DGREP_OK) return rc;
+    if ((rc = win_fail(s, win_collect(s, out))) != DGREP_OK) return rc;
+  } else {
+    s->finished = true;
+    if ((s->flags & DGREP_STREAM_VALUES) && !(out->value_off = static_cast<uint64_t*>(calloc(1, 8))))
+      return DGREP_E_NOMEM;
+  }
+  win_stats_end(s);
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_stream_stats(dgrep_stream* s, uint64_t* windows, uint64_t* data_bytes, uint64_t* max_carry,
+                                  float* cut_ms) {
+  if (!s) return DGREP_E_INVALID;
+  if (windows) *windows = s->windows;
+  if (data_bytes) *data_bytes = s->cap[0] + s->cap[1];
+  if (max_carry) *max_carry = s->max_carry;
+  if (cut_ms) *cut_ms = s->cut_ms;
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_scan_windowed(dgrep_ctx* c, const uint8_t* data, size_t n, size_t window_bytes,
+                                   dgrep_result* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!c || !out || (n && !data)) return DGREP_E_INVALID;
+  if (!win_window_ok(window_bytes)) {
+    c->err = "window_bytes must be a multiple of 4096 in [4096, 2^40]";
+    return DGREP_E_INVALID;
+  }
+  if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
+  HIPCHK(hipSetDevice(c->device));
+  dgrep_stream* s = nullptr;
+  int rc = win_open(c, window_bytes, 0, &s);
+  dgrep_stream_result r;
+  memset(&r, 0, sizeof r);
+  win_stats_begin(s);
+  if (rc == DGREP_OK && !(c->flags & DGREP_DFA_MATCH_NONE)) {
+    if (n) rc = win_fail(s, win_feed(s, data, n));
+    if (rc == DGREP_OK) rc = win_fail(s, win_finish(s));
+    if (rc == DGREP_OK) rc = win_fail(s, win_collect(s, &r));
+  }
+  if (rc == DGREP_OK) win_stats_end(s);
+  const std::string msg = c->err;
+  dgrep_stream_close(s);  // the context holds no stream when the call returns
+  c->err = msg;
+  if (rc != DGREP_OK) return rc;
+  out->count = r.count;
+  out->line_no = r.line_no;
+  out->start = r.start;
+  out->len = r.len;
   return DGREP_OK;
 }
 

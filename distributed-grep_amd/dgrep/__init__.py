@@ -61,7 +61,10 @@ EXPORTS = (
     "dgrep_map_partitions_batch", "dgrep_batch_partitions_free", "dgrep_encode_batch_device",
     "dgrep_reduce_batch", "dgrep_reduce_batch_free", "dgrep_reduce_batch_device", "dgrep_grep_job",
     "dgrep_last_reduce_ms",
+    "dgrep_scan_windowed", "dgrep_stream_open", "dgrep_stream_feed", "dgrep_stream_finish",
+    "dgrep_stream_result_free", "dgrep_stream_close", "dgrep_stream_stats",
 )
+STREAM_VALUES = 1
 COMM_ID_BYTES = 128
 
 STEPPERS = {0: "table", 1: "sheng", 3: "pair", 4: "filter"}
@@ -82,6 +85,12 @@ class UnsupportedPattern(DgrepError):
 class _Result(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint64), ("line_no", ctypes.POINTER(ctypes.c_uint64)),
                 ("start", ctypes.POINTER(ctypes.c_uint64)), ("len", ctypes.POINTER(ctypes.c_uint64))]
+
+
+class _StreamResult(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_uint64), ("line_no", ctypes.POINTER(ctypes.c_uint64)),
+                ("start", ctypes.POINTER(ctypes.c_uint64)), ("len", ctypes.POINTER(ctypes.c_uint64)),
+                ("value_off", ctypes.POINTER(ctypes.c_uint64)), ("values", ctypes.c_void_p)]
 
 
 class _Partitions(ctypes.Structure):
@@ -248,6 +257,21 @@ def lib() -> ctypes.CDLL:
             L.dgrep_grep_job.restype = i
             L.dgrep_last_reduce_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
             L.dgrep_last_reduce_ms.restype = i
+            L.dgrep_scan_windowed.argtypes = [vp, vp, sz, sz, ctypes.POINTER(_Result)]
+            L.dgrep_scan_windowed.restype = i
+            L.dgrep_stream_open.argtypes = [vp, sz, ctypes.c_uint32, ctypes.POINTER(vp)]
+            L.dgrep_stream_open.restype = i
+            L.dgrep_stream_feed.argtypes = [vp, vp, sz, ctypes.POINTER(_StreamResult)]
+            L.dgrep_stream_feed.restype = i
+            L.dgrep_stream_finish.argtypes = [vp, ctypes.POINTER(_StreamResult)]
+            L.dgrep_stream_finish.restype = i
+            L.dgrep_stream_result_free.argtypes = [ctypes.POINTER(_StreamResult)]
+            L.dgrep_stream_result_free.restype = None
+            L.dgrep_stream_close.argtypes = [vp]
+            L.dgrep_stream_close.restype = None
+            L.dgrep_stream_stats.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                             ctypes.POINTER(ctypes.c_float)]
+            L.dgrep_stream_stats.restype = i
             _lib = L
     return _lib
 
@@ -394,6 +418,30 @@ class Context:
             return ln, st, le
         finally:
             self._L.dgrep_result_free(ctypes.byref(res))
+
+    def scan_windowed(self, contents, window: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """scan() with the split never resident as a whole (dgrep_scan_windowed):
+        the same three arrays, from windows of `window` bytes (a multiple of 4096)."""
+        if isinstance(contents, str):
+            contents = contents.encode("utf-8", "surrogateescape")
+        buf = np.frombuffer(contents, dtype=np.uint8) if len(contents) else np.zeros(1, np.uint8)
+        res = _Result()
+        self._check(self._L.dgrep_scan_windowed(self._h, ctypes.c_void_p(buf.ctypes.data), len(contents), window,
+                                                ctypes.byref(res)))
+        try:
+            n = int(res.count)
+            if n == 0:
+                return np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint64)
+            return (np.ctypeslib.as_array(res.line_no, shape=(n,)).copy(),
+                    np.ctypeslib.as_array(res.start, shape=(n,)).copy(),
+                    np.ctypeslib.as_array(res.len, shape=(n,)).copy())
+        finally:
+            self._L.dgrep_result_free(ctypes.byref(res))
+
+    def stream(self, window: int, values: bool = False) -> "Stream":
+        """A stream over this context's loaded pattern (dgrep_stream_open): feed
+        it a split piece by piece. Close it before the context."""
+        return Stream(self, window, values)
 
     def scan_device(self, d_data: int, n: int, d_line: int, d_start: int, d_len: int, capacity: int) -> int:
         """HBM-resident split at device pointer d_data; returns the match count."""
@@ -641,6 +689,73 @@ class Context:
         return d
 
 
+class Stream:
+    """dgrep_stream_*: a split fed in pieces of any length. feed(piece) and
+    finish() return (line_no u64[], start u64[], len u64[]) of the matching
+    lines the call completed, numbered and placed in the whole stream, plus --
+    with values=True -- a list of those lines' bytes (gathered on the device)."""
+
+    def __init__(self, ctx: "Context", window: int, values: bool = False):
+        self._L = lib()
+        self.ctx = ctx
+        self.values = bool(values)
+        h = ctypes.c_void_p()
+        self._h = h
+        ctx._check(self._L.dgrep_stream_open(ctx._h, window, STREAM_VALUES if values else 0, ctypes.byref(h)))
+
+    def _take(self, res: "_StreamResult"):
+        try:
+            n = int(res.count)
+            arr = lambda p: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+            out = (arr(res.line_no), arr(res.start), arr(res.len))
+            if not self.values:
+                return out
+            off = np.ctypeslib.as_array(res.value_off, shape=(n + 1,)).tolist()
+            raw = ctypes.string_at(res.values, off[n]) if off[n] else b""
+            return out + ([raw[off[r]:off[r + 1]] for r in range(n)],)
+        finally:
+            self._L.dgrep_stream_result_free(ctypes.byref(res))
+
+    def feed(self, piece):
+        piece = piece.encode("utf-8", "surrogateescape") if isinstance(piece, str) else piece
+        buf = np.frombuffer(piece, dtype=np.uint8) if len(piece) else np.zeros(1, np.uint8)
+        res = _StreamResult()
+        self.ctx._check(self._L.dgrep_stream_feed(self._h, ctypes.c_void_p(buf.ctypes.data), len(piece),
+                                                  ctypes.byref(res)))
+        return self._take(res)
+
+    def finish(self):
+        res = _StreamResult()
+        self.ctx._check(self._L.dgrep_stream_finish(self._h, ctypes.byref(res)))
+        return self._take(res)
+
+    def stats(self) -> dict:
+        """dgrep_stream_stats: windows scanned, device bytes of the two window
+        buffers now, the longest carried tail, the cut passes' device ms."""
+        w, d, m, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_float()
+        self.ctx._check(self._L.dgrep_stream_stats(self._h, ctypes.byref(w), ctypes.byref(d), ctypes.byref(m),
+                                                   ctypes.byref(ms)))
+        return {"windows": int(w.value), "data_bytes": int(d.value), "max_carry": int(m.value),
+                "cut_ms": float(ms.value)}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value and self.ctx._h.value:
+            self._L.dgrep_stream_close(self._h)
+        self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def build_info() -> str:
     """dgrep_build_info(): "head=<commit>[-dirty] arch=gfx950 hipflags=..."."""
     return lib().dgrep_build_info().decode()
@@ -797,6 +912,26 @@ def Map(filename: str, contents) -> List[KeyValue]:
         kva.append(KeyValue(format_key(filename, n), v.decode("utf-8", "surrogateescape")
                             if isinstance(contents, str) else v))
     return kva
+
+
+def MapStream(filename: str, pieces, window: int = 64 << 20) -> List[KeyValue]:
+    """Map(filename, b"".join(pieces)) for a worker that reads its task file
+    piece by piece and never holds it whole (dgrep_stream_*): every piece is fed
+    as it comes, and the Values are the line bytes the device gathered, not
+    slices of host copies of the pieces. `pieces`: an iterable of bytes (Values
+    are bytes) or of str (Values are str)."""
+    kva = []
+    text = False
+    with _context().stream(window, values=True) as st:
+        def take(res):
+            ln, _, _, vals = res
+            for n, v in zip(ln.tolist(), vals):
+                kva.append((n, v))
+        for piece in pieces:
+            text = text or isinstance(piece, str)
+            take(st.feed(piece))
+        take(st.finish())
+    return [KeyValue(format_key(filename, n), v.decode("utf-8", "surrogateescape") if text else v) for n, v in kva]
 
 
 def MapBatch(files: Sequence[Tuple[str, object]]) -> List[List[KeyValue]]:

@@ -294,6 +294,78 @@ int dgrep_scan_batch_device(dgrep_ctx* ctx, const void* d_packed, size_t n_packe
  * per-split ranges + rebase of the records. */
 int dgrep_last_batch_ms(dgrep_ctx* ctx, float* newline_ms, float* rebase_ms);
 
+/* ---- a split consumed in windows: any size in a fixed device footprint -------
+ * The reference makes one map task per input file, so a split is one unbounded
+ * string (map_reduce/worker.go:72-76), and dgrep_scan keeps all of it in HBM.
+ * The windowed forms consume the split in windows of window_bytes: the device
+ * holds two window buffers, and while one is scanned the next piece is DMA'd
+ * into the other. A window's bytes up to its last '\n' are exactly the lines
+ * it completed (strings.Split of that region, the '\n' excluded); what follows
+ * the '\n' is the unfinished line and is carried to the front of the other
+ * buffer. Records are rebased by the running byte and line counts, so the
+ * result is bit for bit dgrep_scan's on the concatenated bytes, however the
+ * stream is cut. A window without a '\n' completes no line and the buffers
+ * grow by it: the device footprint is bounded by the window plus the longest
+ * unfinished line, not by the split. (Carrying a DFA state across windows, so
+ * that one giant line stays bounded too, is not done.)
+ *
+ * window_bytes: a multiple of 4096 in [4096, 2^40], else DGREP_E_INVALID.
+ * Ingest goes through dgrep_scan's staging ring and the dgrep_set_ingest
+ * settings; a window below 4 MiB takes one pageable copy.
+ * Afterwards dgrep_last_scan_stats reports, over the call's windows, the sums
+ * of matches, tiles, overflow_lanes, candidates, pending, scan_attempts, the
+ * long-line tallies (the 32-bit ones saturate) and the three ms fields;
+ * stepper, lane_chunk and lane_slots are the last non-empty window's.
+ * dgrep_last_kernel_ms is the sum over the windows. */
+
+/* dgrep_scan with the split never resident as a whole: bit for bit dgrep_scan's
+ * result. The one-shot over dgrep_stream_open, _feed(data, n), _finish without
+ * values; the context holds no stream when it returns. Argument checks as
+ * dgrep_scan's (result zeroed), plus window_bytes. */
+int dgrep_scan_windowed(dgrep_ctx* ctx, const uint8_t* data, size_t n, size_t window_bytes, dgrep_result* out);
+
+/* The streaming form, for a caller that never holds the whole split: feed the
+ * pieces as they are read, take each call's completed matching lines. A stream
+ * belongs to its context (one call at a time per context, as everywhere) and is
+ * closed before it. */
+typedef struct dgrep_stream dgrep_stream;
+enum { DGREP_STREAM_VALUES = 1u << 0 }; /* also return the matching lines' bytes */
+typedef struct {
+  uint64_t count;      /* lines COMPLETED by this call that match */
+  uint64_t* line_no;   /* 1-based in the whole stream */
+  uint64_t* start;     /* byte offset in the whole stream */
+  uint64_t* len;
+  uint64_t* value_off; /* count + 1, only with DGREP_STREAM_VALUES, else NULL */
+  uint8_t* values;     /* line r = values[value_off[r] : value_off[r+1]) */
+} dgrep_stream_result;
+/* DGREP_E_INVALID before any GPU call: a null ctx or stream pointer, unknown
+ * flag bits, a bad window_bytes. No DFA loaded: DGREP_E_NO_DFA. */
+int dgrep_stream_open(dgrep_ctx* ctx, size_t window_bytes, uint32_t flags, dgrep_stream** stream);
+/* A feed may have any length: n == 0 does nothing, a feed longer than the
+ * window is cut internally, and one result holds every line the feed completed
+ * (the line a feed's last '\n' ends included; the bytes after it wait for the
+ * next call). `data` is borrowed for the call only. DGREP_E_INVALID, result
+ * zeroed, before any GPU call: a null stream or out, n without data, a feed
+ * after dgrep_stream_finish, and a dgrep_load_dfa on the context since the
+ * stream was opened (with a message). A DGREP_DFA_MATCH_NONE pattern returns
+ * count 0 and copies nothing. A HIP error or out-of-memory mid-stream leaves
+ * the stream unusable: every later call returns the same status;
+ * dgrep_stream_close stays safe. */
+int dgrep_stream_feed(dgrep_stream* stream, const uint8_t* data, size_t n, dgrep_stream_result* out);
+/* The stream's last line: its record if it matches, else nothing. That line
+ * may be the empty one after a final '\n', or the one empty line of an empty
+ * stream. */
+int dgrep_stream_finish(dgrep_stream* stream, dgrep_stream_result* out);
+void dgrep_stream_result_free(dgrep_stream_result* r);
+void dgrep_stream_close(dgrep_stream* stream);
+/* windows scanned, device bytes of the two window buffers now, longest carried
+ * tail, cut-pass ms (HIP events) -- over the stream's life; any pointer may be
+ * NULL. The carried tail is measured to the end of its line: max_carry is the
+ * length of the longest line that lay across a window boundary (or of the
+ * unfinished tail, while that is longer). */
+int dgrep_stream_stats(dgrep_stream* stream, uint64_t* windows, uint64_t* data_bytes, uint64_t* max_carry,
+                       float* cut_ms);
+
 /* ---- whole map tasks over a batch: every split's intermediate files ---------
  * A map task ends at its files mr-<task>-<p>, one per reduce partition
  * (map_reduce/worker.go:78-109). The batch form of dgrep_map_partitions writes
