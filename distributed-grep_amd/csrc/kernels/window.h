@@ -13,8 +13,8 @@
 //
 // A window with no '\n' completes no line: all of fill is carried, so the
 // device footprint is bounded by the window plus the longest unfinished line,
-// not by the split. Carrying a DFA state across windows, so that even one giant
-// line stays bounded, is out of scope.
+// not by the split. A bounded stream (carry.h) folds such a window into the
+// line's DFA state instead, so that even one giant line stays bounded.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -21,6 +21,7 @@
 #include "../../../include/dgrep.h"
 #include "../../../include/dgrep_blob.h"
 #include "../kernels/batch.h"
+#include "../kernels/carry.h"
 #include "../kernels/encode.h"
 #include "../kernels/encode_batch.h"
 #include "../kernels/reduce.h"
@@ -248,6 +249,17 @@ struct dgrep_ctx {
   uint64_t rb_off_cap = 0;
   hipEvent_t evr0 = nullptr, evr1 = nullptr;
   float last_reduce_ms = 0.f;
+
+  // The blob's plain DFA, kept on the host for a bounded stream's carry walk
+  // (kernels/carry.h): uploaded the first time a stream folds, so a context
+  // that never folds pays only these host bytes.
+  std::vector<uint32_t> h_trans;
+  uint8_t h_cls[256] = {};
+  uint32_t h_nstates = 0, h_nclasses = 0, h_start = 0, h_start_m = 0;
+  void* d_carry_trans = nullptr;
+  uint8_t* d_carry_aux = nullptr;  // cls [256], then absorbing [nstates]
+  CarryTable carry;
+  bool carry_ready = false;
 };
 
 // the kind handed to the scan entry points: the stepper, with kKindW32 for the
@@ -570,7 +582,7 @@ extern "C" void dgrep_close(dgrep_ctx* c) {
                   c->d_overflow, c->d_data, c->d_res_line, c->d_res_start, c->d_res_len, c->d_enc_scratch,
                   c->d_fname, c->d_bounds, c->d_enc_out, c->d_red_scratch, c->d_red_out, c->d_bat_begin,
                   c->d_bat_lines, c->d_bat_sums, c->d_res_split, c->d_res_sbegin, c->d_bat_names, c->d_bat_cells,
-                  c->d_rb_seg, c->d_rb_off};
+                  c->d_rb_seg, c->d_rb_off, c->d_carry_trans, c->d_carry_aux};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
@@ -844,6 +856,18 @@ extern "C" int dgrep_load_dfa(dgrep_ctx* c, const void* blob, size_t n) {
     c->long_start_m = h.start_m;
   }
   c->empty_line_matches = trans[size_t(h.start) * h.nclasses + h.byte_class[uint8_t('\n')]] == h.start_m;
+  // the plain DFA for the carry walk: the device copy of the pattern before goes now
+  if (c->d_carry_trans) HIPCHK(hipFree(c->d_carry_trans));
+  if (c->d_carry_aux) HIPCHK(hipFree(c->d_carry_aux));
+  c->d_carry_trans = nullptr;
+  c->d_carry_aux = nullptr;
+  c->carry_ready = false;
+  c->h_trans.assign(trans, trans + size_t(h.nstates) * h.nclasses);
+  memcpy(c->h_cls, h.byte_class, 256);
+  c->h_nstates = h.nstates;
+  c->h_nclasses = h.nclasses;
+  c->h_start = h.start;
+  c->h_start_m = h.start_m;
   int bpc = 0;
   HIPCHK(scan_dfa_occupancy(launch_kind(c), c->table_bytes, &bpc));
   c->blocks_per_cu = std::max(1, std::min(bpc, DGREP_MAX_WG_PER_CU));
@@ -1799,7 +1823,27 @@ struct dgrep_stream {
   // the call's scan stats, summed over its windows
   dgrep_scan_stats agg{};
   float agg_ms = 0.f;
+  // DGREP_STREAM_BOUNDED (kernels/carry.h): a line that outgrew the window is
+  // folded into its DFA state. While `carrying`, the unfinished line is the
+  // folded bytes [line_start, byte_base) of the stream, kept only as the state
+  // in d_carry, plus the tail buf[cur][0 : fill).
+  bool carrying = false;
+  uint64_t line_start = 0;
+  // device, one allocation: the walks' counters [2] u64, then the carried state
+  // and the last walk's two verdicts, u32; pinned: the verdicts
+  unsigned long long* d_carry = nullptr;
+  uint32_t* h_verdict = nullptr;
+  uint32_t* d_pairs = nullptr;  // the walk's (guess, exit) scratch
+  uint64_t pairs_cap = 0;
+  hipEvent_t ev_w0 = nullptr, ev_w1 = nullptr;  // the last walk
+  hipEvent_t ev_v = nullptr;                     // the verdicts' copy to the host
+  bool walk_untimed = false;                     // ev_w0 / ev_w1 are recorded and not yet added to walk_ms
+  uint64_t folds = 0, folded_bytes = 0, chunks = 0;
+  float walk_ms = 0.f;
 };
+
+static uint32_t* carry_state(dgrep_stream* s) { return reinterpret_cast<uint32_t*>(s->d_carry + 2); }
+static uint32_t* carry_verdict(dgrep_stream* s) { return carry_state(s) + 1; }
 
 static uint32_t sat_add32(uint32_t a, uint32_t b) { return uint32_t(std::min<uint64_t>(uint64_t(a) + b, UINT32_MAX)); }
 
@@ -1933,10 +1977,100 @@ static int win_acc_reserve(dgrep_stream* s, uint64_t need) {
   return DGREP_OK;
 }
 
+// The loaded pattern's plain DFA on the device, from the host copy
+// dgrep_load_dfa kept: once per pattern, at the first fold.
+static int carry_ensure(dgrep_ctx* c) {
+  if (c->carry_ready) return DGREP_OK;
+  const uint32_t S = c->h_nstates, K = c->h_nclasses, nl = c->h_cls[uint8_t('\n')];
+  const size_t ne = size_t(S) * K;
+  const bool u32 = S > 65535;
+  const std::vector<uint8_t> absorbing = carry_absorbing(c->h_trans.data(), S, K, nl);
+  std::vector<uint8_t> aux(256 + size_t(S));
+  memcpy(aux.data(), c->h_cls, 256);
+  memcpy(aux.data() + 256, absorbing.data(), S);
+  std::vector<uint16_t> t16;
+  const void* src = c->h_trans.data();
+  size_t bytes = ne * 4;
+  if (!u32) {
+    t16.resize(ne);
+    for (size_t i = 0; i < ne; ++i) t16[i] = uint16_t(c->h_trans[i]);
+    src = t16.data();
+    bytes = ne * 2;
+  }
+  if (!c->d_carry_trans) HIPCHK(hipMalloc(&c->d_carry_trans, std::max<size_t>(bytes, 16)));
+  if (!c->d_carry_aux) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_carry_aux), aux.size()));
+  HIPCHK(hipMemcpy(c->d_carry_trans, src, bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(c->d_carry_aux, aux.data(), aux.size(), hipMemcpyHostToDevice));
+  CarryTable& t = c->carry;
+  t.trans = c->d_carry_trans;
+  t.cls = c->d_carry_aux;
+  t.absorbing = c->d_carry_aux + 256;
+  t.nstates = S;
+  t.nclasses = K;
+  t.start = c->h_start;
+  t.start_m = c->h_start_m;
+  t.nl_class = nl;
+  t.u32 = u32;
+  carry_seeds(absorbing, S, c->h_start, t.seed);
+  c->carry_ready = true;
+  return DGREP_OK;
+}
+
+// the last walk's device time, once the host knows it is done
+static int carry_ms_take(dgrep_stream* s) {
+  dgrep_ctx* c = s->c;
+  if (!s->walk_untimed) return DGREP_OK;
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, s->ev_w0, s->ev_w1));
+  s->walk_ms += ms;
+  s->walk_untimed = false;
+  return DGREP_OK;
+}
+
+// Queue the walk of d[0 : m) (no '\n' in it) from the carried state, or from
+// `start` if no line is carried; the carried state becomes the walk's exit.
+// want_verdict: the verdicts go to h_verdict, valid once ev_v is done. No host
+// wait, unless the walk before was never waited for.
+static int win_walk(dgrep_stream* s, const uint8_t* d, uint64_t m, bool want_verdict, bool dual) {
+  dgrep_ctx* c = s->c;
+  int rc;
+  if ((rc = carry_ensure(c)) != DGREP_OK) return rc;
+  if (s->walk_untimed) {
+    HIPCHK(hipEventSynchronize(s->ev_w1));
+    if ((rc = carry_ms_take(s)) != DGREP_OK) return rc;
+  }
+  const bool rows_in_lds = uint64_t(c->h_nstates) * c->h_nclasses * (c->carry.u32 ? 4 : 2) <= kCarryRowsLds;
+  const CarryPlan plan = carry_plan(m, carry_lanes(m, uint64_t(std::max(c->num_cus, 1)), rows_in_lds));
+  if ((rc = grow(c, &s->d_pairs, &s->pairs_cap, carry_pairs_bytes(plan) / 4)) != DGREP_OK) return rc;
+  CarryWalk w;
+  w.data = d;
+  w.m = m;
+  w.state = carry_state(s);
+  w.from_start = !s->carrying;
+  w.verdict = want_verdict ? carry_verdict(s) : nullptr;
+  w.dual = dual;
+  w.pairs = s->d_pairs;
+  w.counters = s->d_carry;
+  HIPCHK(hipEventRecord(s->ev_w0, c->stream));
+  HIPCHK(carry_walk(c->carry, w, plan, c->stream));
+  HIPCHK(hipEventRecord(s->ev_w1, c->stream));
+  s->walk_untimed = true;
+  s->chunks += plan.nchunks;
+  if (want_verdict) {
+    HIPCHK(hipMemcpyAsync(s->h_verdict, carry_verdict(s), 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(s->ev_v, c->stream));
+  }
+  return DGREP_OK;
+}
+
 // One window's completed lines d[0 : n) (16-byte aligned; n may be 0, the one
 // empty line): scan, then the records rebased and appended to the call's, then
-// their bytes gathered.
-static int win_scan(dgrep_stream* s, const uint8_t* d, uint64_t n) {
+// their bytes gathered. `splice` (a bounded stream that carries a line): the
+// region's line 1, d[0 : head), is the end of the carried line; its walk is
+// queued with both verdicts wanted. The scan judged the head as a line of its
+// own: that record is dropped, and the carried line's takes its place if the
+// walk from the carried state says so.
+static int win_scan(dgrep_stream* s, const uint8_t* d, uint64_t n, bool splice = false, uint64_t head = 0) {
   dgrep_ctx* c = s->c;
   int rc;
   uint64_t count = 0;
@@ -1950,6 +2084,29 @@ static int win_scan(dgrep_stream* s, const uint8_t* d, uint64_t n) {
   }
   win_stats_add(s, n);
   ++s->windows;
+  if (splice) {
+    // the verdicts were queued before the scan: behind the scan's own host wait this one returns at once
+    HIPCHK(hipEventSynchronize(s->ev_v));
+    if ((rc = carry_ms_take(s)) != DGREP_OK) return rc;
+    const uint64_t ins = s->h_verdict[0] ? 1 : 0, drop = s->h_verdict[1] ? 1 : 0;
+    if (drop > count) {
+      c->err = "bounded stream: the scan and the walk disagree on the carried line's end";
+      return DGREP_E_HIP;
+    }
+    s->agg.matches = s->agg.matches - drop + ins;
+    const uint64_t kept = count - drop;
+    if (kept + ins == 0) return DGREP_OK;
+    if ((rc = win_acc_reserve(s, s->nrec + kept + ins)) != DGREP_OK) return rc;
+    if (ins)
+      HIPCHK(carry_put_record(s->d_line + s->nrec, s->d_start + s->nrec, s->d_len + s->nrec, s->line_base + 1,
+                              s->line_start, s->byte_base + head - s->line_start, c->stream));
+    s->nrec += ins;
+    HIPCHK(window_rebase_append(c->d_res_line + drop, c->d_res_start + drop, c->d_res_len + drop, kept, s->line_base,
+                                s->byte_base, s->d_line + s->nrec, s->d_start + s->nrec, s->d_len + s->nrec,
+                                c->num_cus, c->stream));
+    s->nrec += kept;
+    return DGREP_OK;  // a bounded stream returns no values
+  }
   if (count == 0) return DGREP_OK;
   if ((rc = win_acc_reserve(s, s->nrec + count)) != DGREP_OK) return rc;
   HIPCHK(window_rebase_append(c->d_res_line, c->d_res_start, c->d_res_len, count, s->line_base, s->byte_base,
@@ -2032,10 +2189,37 @@ static int win_feed(dgrep_stream* s, const uint8_t* data, size_t n) {
       return DGREP_E_HIP;
     }
     const uint64_t next = std::min<uint64_t>(s->window, n - off);
+    if ((rc = carry_ms_take(s)) != DGREP_OK) return rc;  // a walk queued before this window's cut is done
+    if (last1 == 0 && (s->flags & DGREP_STREAM_BOUNDED) && F >= s->window) {
+      // Fold: a full window and no line completed. Its bytes go into the
+      // carried state and are forgotten; the next piece lands at the front of
+      // the other buffer while the walk reads this one. No host wait.
+      if ((rc = win_walk(s, s->buf[s->cur], F, false, false)) != DGREP_OK) return rc;
+      HIPCHK(hipEventRecord(s->ev_free[s->cur], c->stream));
+      if (!s->carrying) s->line_start = s->byte_base;
+      s->carrying = true;
+      s->byte_base += F;
+      ++s->folds;
+      s->folded_bytes += F;
+      s->max_carry = std::max(s->max_carry, s->byte_base - s->line_start);
+      const int o = s->cur ^ 1;
+      HIPCHK(hipStreamWaitEvent(c->copy_stream, s->ev_free[o], 0));
+      if (next) {
+        if ((rc = win_reserve(s, o, next, 0)) != DGREP_OK) return rc;
+        if ((rc = win_ingest(s, s->buf[o], data + off, next)) != DGREP_OK) return rc;
+        off += next;
+      } else {
+        HIPCHK(hipEventRecord(s->ev_in, c->copy_stream));
+      }
+      s->cur = o;
+      s->fill = 0;
+      pending = next;
+      continue;
+    }
     if (last1 == 0) {
       // no line completed: all of it is the tail, and the next piece lands behind it
       s->fill = F;
-      s->max_carry = std::max(s->max_carry, F);
+      s->max_carry = std::max(s->max_carry, s->carrying ? s->byte_base + F - s->line_start : F);
       pending = next;
       if (next) {
         if ((rc = win_reserve(s, s->cur, F + next, F)) != DGREP_OK) return rc;
@@ -2058,7 +2242,23 @@ static int win_feed(dgrep_stream* s, const uint8_t* data, size_t n) {
     } else {
       HIPCHK(hipEventRecord(s->ev_in, c->copy_stream));
     }
-    if ((rc = win_scan(s, s->buf[s->cur], cut)) != DGREP_OK) return rc;
+    if (s->carrying) {
+      // The carried line ends in this window, at the first '\n' (the tail holds
+      // none, so the first one behind it is the first one): walk its last bytes
+      // from the carried state, and from `start` as the scan will.
+      const uint64_t first1 = s->h_cut[2];
+      if (first1 == 0 || first1 > last1) {
+        c->err = "bounded stream: the carried line's end lies outside the window";
+        return DGREP_E_HIP;
+      }
+      const uint64_t head = first1 - 1;
+      if ((rc = win_walk(s, s->buf[s->cur], head, true, true)) != DGREP_OK) return rc;
+      s->max_carry = std::max(s->max_carry, s->byte_base + head - s->line_start);
+      if ((rc = win_scan(s, s->buf[s->cur], cut, true, head)) != DGREP_OK) return rc;
+      s->carrying = false;
+    } else if ((rc = win_scan(s, s->buf[s->cur], cut)) != DGREP_OK) {
+      return rc;
+    }
     HIPCHK(hipEventRecord(s->ev_free[s->cur], c->stream));
     s->byte_base += last1;
     s->line_base += nl;
@@ -2074,7 +2274,27 @@ static int win_feed(dgrep_stream* s, const uint8_t* data, size_t n) {
 static int win_finish(dgrep_stream* s) {
   dgrep_ctx* c = s->c;
   HIPCHK(hipStreamWaitEvent(c->stream, s->ev_in, 0));
-  const int rc = win_scan(s, s->buf[s->cur], s->fill);
+  int rc;
+  if (s->carrying) {
+    // the last line is the carried one: its folded bytes, then the tail
+    if ((rc = win_walk(s, s->buf[s->cur], s->fill, true, false)) != DGREP_OK) return rc;
+    HIPCHK(hipEventSynchronize(s->ev_v));
+    if ((rc = carry_ms_take(s)) != DGREP_OK) return rc;
+    const uint64_t len = s->byte_base + s->fill - s->line_start;
+    s->max_carry = std::max(s->max_carry, len);
+    ++s->windows;
+    if (s->h_verdict[0]) {
+      if ((rc = win_acc_reserve(s, s->nrec + 1)) != DGREP_OK) return rc;
+      HIPCHK(carry_put_record(s->d_line + s->nrec, s->d_start + s->nrec, s->d_len + s->nrec, s->line_base + 1,
+                              s->line_start, len, c->stream));
+      ++s->nrec;
+      ++s->agg.matches;
+    }
+    s->carrying = false;
+    s->finished = true;
+    return DGREP_OK;
+  }
+  rc = win_scan(s, s->buf[s->cur], s->fill);
   if (rc == DGREP_OK) s->finished = true;
   return rc;
 }
@@ -2133,6 +2353,14 @@ static int win_open(dgrep_ctx* c, size_t window_bytes, uint32_t flags, dgrep_str
   HIPCHK(hipEventCreate(&s->ev_c1));
   for (hipEvent_t* e : {&s->ev_free[0], &s->ev_free[1], &s->ev_in})
     HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  if (flags & DGREP_STREAM_BOUNDED) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->d_carry), 32));
+    HIPCHK(hipMemsetAsync(s->d_carry, 0, 32, c->stream));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_verdict), 2 * sizeof(uint32_t), hipHostMallocDefault));
+    HIPCHK(hipEventCreate(&s->ev_w0));
+    HIPCHK(hipEventCreate(&s->ev_w1));
+    HIPCHK(hipEventCreateWithFlags(&s->ev_v, hipEventDisableTiming));
+  }
   return DGREP_OK;
 }
 
@@ -2142,11 +2370,13 @@ extern "C" void dgrep_stream_close(dgrep_stream* s) {
   (void)hipSetDevice(c->device);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  void* bufs[] = {s->buf[0], s->buf[1], s->d_cut, s->d_line, s->d_start, s->d_len, s->d_voff, s->d_values, s->d_gscratch};
+  void* bufs[] = {s->buf[0], s->buf[1], s->d_cut, s->d_line, s->d_start, s->d_len, s->d_voff, s->d_values, s->d_gscratch,
+                  s->d_carry, s->d_pairs};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (s->h_cut) (void)hipHostFree(s->h_cut);
-  for (hipEvent_t e : {s->ev_c0, s->ev_c1, s->ev_free[0], s->ev_free[1], s->ev_in})
+  if (s->h_verdict) (void)hipHostFree(s->h_verdict);
+  for (hipEvent_t e : {s->ev_c0, s->ev_c1, s->ev_free[0], s->ev_free[1], s->ev_in, s->ev_w0, s->ev_w1, s->ev_v})
     if (e) (void)hipEventDestroy(e);
   free(s->h_values);
   delete s;
@@ -2162,14 +2392,32 @@ extern "C" void dgrep_stream_result_free(dgrep_stream_result* r) {
   memset(r, 0, sizeof *r);
 }
 
+static const char kBoundedPartial[] =
+    "a bounded stream carries an exact DFA state: a DGREP_DFA_PARTIAL pattern (over the compiler's state budget) "
+    "has none past CAND";
+
 extern "C" int dgrep_stream_open(dgrep_ctx* c, size_t window_bytes, uint32_t flags, dgrep_stream** out) {
   if (out) *out = nullptr;
-  if (!c || !out || (flags & ~uint32_t(DGREP_STREAM_VALUES))) return DGREP_E_INVALID;
+  if (!c || !out || (flags & ~uint32_t(DGREP_STREAM_VALUES | DGREP_STREAM_BOUNDED))) return DGREP_E_INVALID;
+  const bool bounded = (flags & DGREP_STREAM_BOUNDED) != 0;
+  if (bounded && (flags & DGREP_STREAM_VALUES)) {
+    c->err = "DGREP_STREAM_BOUNDED with DGREP_STREAM_VALUES: a folded line's bytes are gone";
+    return DGREP_E_INVALID;
+  }
   if (!win_window_ok(window_bytes)) {
     c->err = "window_bytes must be a multiple of 4096 in [4096, 2^40]";
     return DGREP_E_INVALID;
   }
+  if (bounded && !c->loaded) {
+    // whether a line's state can be carried is the pattern's property: without one the flag means nothing
+    c->err = "DGREP_STREAM_BOUNDED needs a loaded pattern";
+    return DGREP_E_INVALID;
+  }
   if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
+  if (bounded && (c->flags & DGREP_DFA_PARTIAL)) {
+    c->err = kBoundedPartial;
+    return DGREP_E_UNSUPPORTED;
+  }
   HIPCHK(hipSetDevice(c->device));
   const int rc = win_open(c, window_bytes, flags, out);
   if (rc != DGREP_OK) {
@@ -2255,8 +2503,42 @@ extern "C" int dgrep_stream_stats(dgrep_stream* s, uint64_t* windows, uint64_t* 
   return DGREP_OK;
 }
 
+extern "C" int dgrep_stream_carry_stats(dgrep_stream* s, uint64_t* folds, uint64_t* folded_bytes, uint64_t* chunks,
+                                        uint64_t* guess_misses, float* walk_ms) {
+  if (!s) return DGREP_E_INVALID;
+  dgrep_ctx* c = s->c;
+  unsigned long long ctr[2] = {0, 0};
+  if (s->d_carry && (guess_misses || walk_ms)) {
+    // the misses are counted on the device, and the last walk may still run
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(ctr, s->d_carry, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int rc = carry_ms_take(s);
+    if (rc != DGREP_OK) return rc;
+  }
+  if (folds) *folds = s->folds;
+  if (folded_bytes) *folded_bytes = s->folded_bytes;
+  if (chunks) *chunks = s->chunks;
+  if (guess_misses) *guess_misses = ctr[1];
+  if (walk_ms) *walk_ms = s->walk_ms;
+  return DGREP_OK;
+}
+
+static int scan_windowed_flags(dgrep_ctx* c, const uint8_t* data, size_t n, size_t window_bytes, uint32_t flags,
+                               dgrep_result* out);
+
 extern "C" int dgrep_scan_windowed(dgrep_ctx* c, const uint8_t* data, size_t n, size_t window_bytes,
                                    dgrep_result* out) {
+  return scan_windowed_flags(c, data, n, window_bytes, 0, out);
+}
+
+extern "C" int dgrep_scan_bounded(dgrep_ctx* c, const uint8_t* data, size_t n, size_t window_bytes,
+                                  dgrep_result* out) {
+  return scan_windowed_flags(c, data, n, window_bytes, DGREP_STREAM_BOUNDED, out);
+}
+
+static int scan_windowed_flags(dgrep_ctx* c, const uint8_t* data, size_t n, size_t window_bytes, uint32_t flags,
+                               dgrep_result* out) {
   if (out) memset(out, 0, sizeof *out);
   if (!c || !out || (n && !data)) return DGREP_E_INVALID;
   if (!win_window_ok(window_bytes)) {
@@ -2264,9 +2546,13 @@ extern "C" int dgrep_scan_windowed(dgrep_ctx* c, const uint8_t* data, size_t n, 
     return DGREP_E_INVALID;
   }
   if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
+  if ((flags & DGREP_STREAM_BOUNDED) && (c->flags & DGREP_DFA_PARTIAL)) {
+    c->err = kBoundedPartial;
+    return DGREP_E_UNSUPPORTED;
+  }
   HIPCHK(hipSetDevice(c->device));
   dgrep_stream* s = nullptr;
-  int rc = win_open(c, window_bytes, 0, &s);
+  int rc = win_open(c, window_bytes, flags, &s);
   dgrep_stream_result r;
   memset(&r, 0, sizeof r);
   win_stats_begin(s);

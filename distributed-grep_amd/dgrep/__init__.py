@@ -63,8 +63,10 @@ EXPORTS = (
     "dgrep_last_reduce_ms",
     "dgrep_scan_windowed", "dgrep_stream_open", "dgrep_stream_feed", "dgrep_stream_finish",
     "dgrep_stream_result_free", "dgrep_stream_close", "dgrep_stream_stats",
+    "dgrep_scan_bounded", "dgrep_stream_carry_stats",
 )
 STREAM_VALUES = 1
+STREAM_BOUNDED = 2
 COMM_ID_BYTES = 128
 
 STEPPERS = {0: "table", 1: "sheng", 3: "pair", 4: "filter"}
@@ -272,6 +274,11 @@ def lib() -> ctypes.CDLL:
             L.dgrep_stream_stats.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64),
                                              ctypes.POINTER(ctypes.c_float)]
             L.dgrep_stream_stats.restype = i
+            L.dgrep_scan_bounded.argtypes = [vp, vp, sz, sz, ctypes.POINTER(_Result)]
+            L.dgrep_scan_bounded.restype = i
+            L.dgrep_stream_carry_stats.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                                   ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_float)]
+            L.dgrep_stream_carry_stats.restype = i
             _lib = L
     return _lib
 
@@ -419,15 +426,17 @@ class Context:
         finally:
             self._L.dgrep_result_free(ctypes.byref(res))
 
-    def scan_windowed(self, contents, window: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def scan_windowed(self, contents, window: int, bounded: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """scan() with the split never resident as a whole (dgrep_scan_windowed):
-        the same three arrays, from windows of `window` bytes (a multiple of 4096)."""
+        the same three arrays, from windows of `window` bytes (a multiple of 4096).
+        bounded=True (dgrep_scan_bounded): a line longer than the window is folded
+        into its DFA state instead of growing the window buffers."""
         if isinstance(contents, str):
             contents = contents.encode("utf-8", "surrogateescape")
         buf = np.frombuffer(contents, dtype=np.uint8) if len(contents) else np.zeros(1, np.uint8)
         res = _Result()
-        self._check(self._L.dgrep_scan_windowed(self._h, ctypes.c_void_p(buf.ctypes.data), len(contents), window,
-                                                ctypes.byref(res)))
+        call = self._L.dgrep_scan_bounded if bounded else self._L.dgrep_scan_windowed
+        self._check(call(self._h, ctypes.c_void_p(buf.ctypes.data), len(contents), window, ctypes.byref(res)))
         try:
             n = int(res.count)
             if n == 0:
@@ -438,10 +447,12 @@ class Context:
         finally:
             self._L.dgrep_result_free(ctypes.byref(res))
 
-    def stream(self, window: int, values: bool = False) -> "Stream":
+    def stream(self, window: int, values: bool = False, bounded: bool = False) -> "Stream":
         """A stream over this context's loaded pattern (dgrep_stream_open): feed
-        it a split piece by piece. Close it before the context."""
-        return Stream(self, window, values)
+        it a split piece by piece. Close it before the context. bounded=True
+        (DGREP_STREAM_BOUNDED) keeps the device footprint fixed whatever the
+        lines' lengths; it returns no values."""
+        return Stream(self, window, values, bounded)
 
     def scan_device(self, d_data: int, n: int, d_line: int, d_start: int, d_len: int, capacity: int) -> int:
         """HBM-resident split at device pointer d_data; returns the match count."""
@@ -695,13 +706,15 @@ class Stream:
     lines the call completed, numbered and placed in the whole stream, plus --
     with values=True -- a list of those lines' bytes (gathered on the device)."""
 
-    def __init__(self, ctx: "Context", window: int, values: bool = False):
+    def __init__(self, ctx: "Context", window: int, values: bool = False, bounded: bool = False):
         self._L = lib()
         self.ctx = ctx
         self.values = bool(values)
+        self.bounded = bool(bounded)
         h = ctypes.c_void_p()
         self._h = h
-        ctx._check(self._L.dgrep_stream_open(ctx._h, window, STREAM_VALUES if values else 0, ctypes.byref(h)))
+        flags = (STREAM_VALUES if values else 0) | (STREAM_BOUNDED if bounded else 0)
+        ctx._check(self._L.dgrep_stream_open(ctx._h, window, flags, ctypes.byref(h)))
 
     def _take(self, res: "_StreamResult"):
         try:
@@ -737,6 +750,17 @@ class Stream:
                                                    ctypes.byref(ms)))
         return {"windows": int(w.value), "data_bytes": int(d.value), "max_carry": int(m.value),
                 "cut_ms": float(ms.value)}
+
+    def carry_stats(self) -> dict:
+        """dgrep_stream_carry_stats: a bounded stream's folds, their bytes, the
+        chunks its walks covered, the chunks whose guesses missed, the walks'
+        device ms (all 0 on a stream that is not bounded)."""
+        f, b, ch, gm, ms = (ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(),
+                            ctypes.c_float())
+        self.ctx._check(self._L.dgrep_stream_carry_stats(self._h, ctypes.byref(f), ctypes.byref(b), ctypes.byref(ch),
+                                                         ctypes.byref(gm), ctypes.byref(ms)))
+        return {"folds": int(f.value), "folded_bytes": int(b.value), "chunks": int(ch.value),
+                "guess_misses": int(gm.value), "walk_ms": float(ms.value)}
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value and self.ctx._h.value:

@@ -306,8 +306,24 @@ int dgrep_last_batch_ms(dgrep_ctx* ctx, float* newline_ms, float* rebase_ms);
  * result is bit for bit dgrep_scan's on the concatenated bytes, however the
  * stream is cut. A window without a '\n' completes no line and the buffers
  * grow by it: the device footprint is bounded by the window plus the longest
- * unfinished line, not by the split. (Carrying a DFA state across windows, so
- * that one giant line stays bounded too, is not done.)
+ * unfinished line, not by the split.
+ *
+ * DGREP_STREAM_BOUNDED / dgrep_scan_bounded make the bound unconditional. The
+ * DFA restarts only at '\n' and a line matches iff the state at its end steps
+ * to start_m on '\n' (dgrep_blob.h), so an unfinished line needs only its
+ * state kept. Once a full window of bytes holds no '\n' they are folded: a
+ * device pass walks them from the carried state (from start at the line's
+ * first fold) to the exit state, in parallel and exactly for any DFA, and the
+ * bytes are forgotten. Less than one window is ever carried as bytes, so each
+ * of the two buffers holds fewer than 2 * window_bytes (plus 320 of padding),
+ * whatever the input. When the line's '\n' arrives, its last bytes are walked
+ * from the carried state and the verdict yields the line's one record -- its
+ * start and length reach back over the folded bytes -- in place of what the
+ * window's scan made of those last bytes alone. The records stay bit for bit
+ * dgrep_scan's. A fold adds no host synchronisation. A folded line's bytes are
+ * gone, so a bounded stream returns no values: a worker re-reads them from
+ * start and len. A DGREP_DFA_PARTIAL pattern has no exact state past CAND and
+ * is refused.
  *
  * window_bytes: a multiple of 4096 in [4096, 2^40], else DGREP_E_INVALID.
  * Ingest goes through dgrep_scan's staging ring and the dgrep_set_ingest
@@ -324,12 +340,21 @@ int dgrep_last_batch_ms(dgrep_ctx* ctx, float* newline_ms, float* rebase_ms);
  * dgrep_scan's (result zeroed), plus window_bytes. */
 int dgrep_scan_windowed(dgrep_ctx* ctx, const uint8_t* data, size_t n, size_t window_bytes, dgrep_result* out);
 
+/* dgrep_scan_windowed with lines longer than the window folded into their DFA
+ * state: open(DGREP_STREAM_BOUNDED), feed, finish. The same argument checks and
+ * the same result, bit for bit dgrep_scan's. A DGREP_DFA_PARTIAL pattern:
+ * DGREP_E_UNSUPPORTED with a message. */
+int dgrep_scan_bounded(dgrep_ctx* ctx, const uint8_t* data, size_t n, size_t window_bytes, dgrep_result* out);
+
 /* The streaming form, for a caller that never holds the whole split: feed the
  * pieces as they are read, take each call's completed matching lines. A stream
  * belongs to its context (one call at a time per context, as everywhere) and is
  * closed before it. */
 typedef struct dgrep_stream dgrep_stream;
-enum { DGREP_STREAM_VALUES = 1u << 0 }; /* also return the matching lines' bytes */
+enum {
+  DGREP_STREAM_VALUES = 1u << 0, /* also return the matching lines' bytes */
+  DGREP_STREAM_BOUNDED = 1u << 1 /* fold a line that outgrows the window into its DFA state (see above) */
+};
 typedef struct {
   uint64_t count;      /* lines COMPLETED by this call that match */
   uint64_t* line_no;   /* 1-based in the whole stream */
@@ -339,7 +364,11 @@ typedef struct {
   uint8_t* values;     /* line r = values[value_off[r] : value_off[r+1]) */
 } dgrep_stream_result;
 /* DGREP_E_INVALID before any GPU call: a null ctx or stream pointer, unknown
- * flag bits, a bad window_bytes. No DFA loaded: DGREP_E_NO_DFA. */
+ * flag bits, a bad window_bytes. No DFA loaded: DGREP_E_NO_DFA.
+ * DGREP_STREAM_BOUNDED: with DGREP_STREAM_VALUES it is DGREP_E_INVALID (a
+ * folded line's bytes are gone); it is a property of the loaded pattern, so
+ * without one it is DGREP_E_INVALID as well, and with a DGREP_DFA_PARTIAL
+ * pattern DGREP_E_UNSUPPORTED -- each with a message and no stream. */
 int dgrep_stream_open(dgrep_ctx* ctx, size_t window_bytes, uint32_t flags, dgrep_stream** stream);
 /* A feed may have any length: n == 0 does nothing, a feed longer than the
  * window is cut internally, and one result holds every line the feed completed
@@ -365,6 +394,15 @@ void dgrep_stream_close(dgrep_stream* stream);
  * unfinished tail, while that is longer). */
 int dgrep_stream_stats(dgrep_stream* stream, uint64_t* windows, uint64_t* data_bytes, uint64_t* max_carry,
                        float* cut_ms);
+/* A bounded stream's folds over its life (all 0 on any other stream): windows
+ * folded, their bytes, chunks walked (folds, line ends and the finish), chunks
+ * whose guesses missed the true entry state and were walked again, and the
+ * walks' device time (ms, HIP events). Any pointer may be NULL. With a bounded
+ * stream max_carry above is still the true length of the longest line across a
+ * window boundary, folded bytes included. Asking for guess_misses or walk_ms
+ * waits for the stream's queued work. */
+int dgrep_stream_carry_stats(dgrep_stream* stream, uint64_t* folds, uint64_t* folded_bytes, uint64_t* chunks,
+                             uint64_t* guess_misses, float* walk_ms);
 
 /* ---- whole map tasks over a batch: every split's intermediate files ---------
  * A map task ends at its files mr-<task>-<p>, one per reduce partition
