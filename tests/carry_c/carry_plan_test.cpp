@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "carry_plan.h"
@@ -101,7 +102,65 @@ static Dfa random_dfa(uint32_t S, uint32_t K, bool counter) {
   return d;
 }
 
-int main() {
+// `carry_plan_test print`: what carry_plan.h computes for inputs written out
+// here and, the same, in tests/test_carry_plan.py, which compares these lines
+// with tests/carry_cases.py's restatement of the four functions.
+static const uint64_t kPrintM[] = {0,      1,      255,     256,     257,     4095,    4096,    4097,    16383,
+                                   16384,  65535,  65536,   65537,   131071,  131072,  131073,  262143,  262144,
+                                   262145, 524289, 1048575, 1048576, 1048577, 2097151, 2097152, 2097153, 268435456,
+                                   (uint64_t(1) << 32) + 1, uint64_t(1) << 40};
+static const uint64_t kPrintCus[] = {0, 1, 4, 256, 304};
+
+// [nstates][nclasses]; the class of '\n' is 1 in both
+static const uint32_t kTableA[6][3] = {{1, 0, 2}, {1, 0, 1}, {2, 5, 2}, {3, 3, 3}, {4, 0, 4}, {0, 1, 2}};
+static const uint32_t kTableB[9][2] = {{0, 3}, {1, 1}, {2, 0}, {3, 4}, {5, 0}, {5, 5}, {6, 1}, {7, 2}, {1, 8}};
+
+template <uint32_t S, uint32_t K>
+static void print_table(const char* name, const uint32_t (&t)[S][K], uint32_t nl) {
+  const std::vector<uint8_t> a = carry_absorbing(&t[0][0], S, K, nl);
+  printf("absorbing %s", name);
+  for (uint32_t x = 0; x < S; ++x) printf(" %u", unsigned(a[x]));
+  printf("\n");
+  for (uint32_t start = 0; start < S; ++start) {
+    uint32_t seed[kCarryGuesses];
+    carry_seeds(a, S, start, seed);
+    printf("seeds %s %u: %u %u %u %u\n", name, start, seed[0], seed[1], seed[2], seed[3]);
+  }
+  // fewer states than guesses: the first n rows as a table of their own (every entry taken modulo n)
+  for (uint32_t n = 1; n <= 3; ++n) {
+    std::vector<uint32_t> small(size_t(n) * K);
+    for (uint32_t x = 0; x < n; ++x)
+      for (uint32_t k = 0; k < K; ++k) small[size_t(x) * K + k] = t[x][k] % n;
+    const std::vector<uint8_t> sa = carry_absorbing(small.data(), n, K, nl);
+    uint32_t seed[kCarryGuesses];
+    carry_seeds(sa, n, n - 1, seed);
+    printf("small %s %u:", name, n);
+    for (uint32_t x = 0; x < n; ++x) printf(" %u", unsigned(sa[x]));
+    printf(" : %u %u %u %u\n", seed[0], seed[1], seed[2], seed[3]);
+  }
+}
+
+static int print_mode() {
+  for (uint64_t m : kPrintM)
+    for (uint64_t cus : kPrintCus)
+      for (int lds = 1; lds >= 0; --lds) {
+        const uint64_t lanes = carry_lanes(m, cus, lds != 0);
+        const CarryPlan p = carry_plan(m, lanes);
+        printf("plan %llu %llu %d: %llu %llu %llu\n", (unsigned long long)m, (unsigned long long)cus, lds,
+               (unsigned long long)lanes, (unsigned long long)p.chunk, (unsigned long long)p.nchunks);
+      }
+  for (uint64_t lanes : {uint64_t(0), uint64_t(1), uint64_t(3), uint64_t(64)}) {
+    const CarryPlan p = carry_plan(100000, lanes);
+    printf("lanes %llu: %llu %llu\n", (unsigned long long)lanes, (unsigned long long)p.chunk,
+           (unsigned long long)p.nchunks);
+  }
+  print_table("A", kTableA, 1);
+  print_table("B", kTableB, 1);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::string(argv[1]) == "print") return print_mode();
   // the plan alone, at sizes no buffer could have
   for (uint64_t m : {uint64_t(0), uint64_t(1), uint64_t(255), uint64_t(256), uint64_t(257), uint64_t(1) << 20,
                      (uint64_t(1) << 41) - 1, ~uint64_t(0) >> 1, ~uint64_t(0)})
