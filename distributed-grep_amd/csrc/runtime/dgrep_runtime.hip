@@ -24,6 +24,7 @@
 #include "../kernels/carry.h"
 #include "../kernels/encode.h"
 #include "../kernels/encode_batch.h"
+#include "../kernels/encode_window.h"
 #include "../kernels/reduce.h"
 #include "../kernels/reduce_batch.h"
 #include "../kernels/scan_common.h"
@@ -215,6 +216,7 @@ struct dgrep_ctx {
   uint8_t* d_enc_out = nullptr;
   uint64_t enc_out_cap = 0;
   float last_encode_ms = 0.f;
+  uint32_t long_value = 0;  // dgrep_set_long_value: 0 = kLongValueDefault (the window encoder only)
 
   // many splits in one scan (dgrep_scan_batch*, kernels/batch.h)
   uint64_t* d_bat_begin = nullptr;  // [k + 1]
@@ -625,6 +627,16 @@ extern "C" int dgrep_set_lane_chunk(dgrep_ctx* c, uint32_t chunk_bytes) {
     return DGREP_E_INVALID;
   }
   c->lane_chunk = chunk_bytes;
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_set_long_value(dgrep_ctx* c, uint32_t bytes) {
+  if (!c) return DGREP_E_INVALID;
+  if (bytes && (bytes % 64 || bytes < 256 || bytes > (1u << 30))) {
+    c->err = "long value must be 0 or a multiple of 64 in [256, 2^30]";
+    return DGREP_E_INVALID;
+  }
+  c->long_value = bytes;
   return DGREP_OK;
 }
 
@@ -1840,6 +1852,29 @@ struct dgrep_stream {
   bool walk_untimed = false;                     // ev_w0 / ev_w1 are recorded and not yet added to walk_ms
   uint64_t folds = 0, folded_bytes = 0, chunks = 0;
   float walk_ms = 0.f;
+  // A partition stream (dgrep_stream_open_partitions, kernels/encode_window.h):
+  // every window's records are encoded where they lie, in the window buffer,
+  // into d_enc -- one window's bytes at a time -- and copied to the host
+  // accumulator as one row of cells. No record array is kept.
+  bool parts = false;
+  uint32_t nreduce = 0;
+  uint32_t key_hash0 = 0, fname_json_len = 0;
+  uint8_t* d_fname = nullptr;  // the filename, JSON-escaped
+  uint8_t* d_enc = nullptr;
+  uint64_t enc_cap = 0;
+  uint8_t* d_pscratch = nullptr;
+  uint64_t pscratch_cap = 0;
+  uint64_t* d_pbounds = nullptr;  // [2 nreduce + 2]
+  std::vector<uint64_t> h_pbounds;
+  hipEvent_t ev_e0 = nullptr, ev_e1 = nullptr;
+  // the call's rows so far (host)
+  uint8_t* h_cells = nullptr;
+  uint64_t h_cells_cap = 0, cell_bytes = 0;
+  std::vector<uint64_t> cell_off;  // rows * nreduce + 1 once a row exists
+  float call_encode_ms = 0.f;
+  // dgrep_stream_partition_stats
+  uint64_t rows = 0, out_bytes = 0, long_values = 0;
+  float encode_ms = 0.f;
 };
 
 static uint32_t* carry_state(dgrep_stream* s) { return reinterpret_cast<uint32_t*>(s->d_carry + 2); }
@@ -1851,6 +1886,7 @@ static void win_stats_begin(dgrep_stream* s) {
   s->agg = dgrep_scan_stats{};
   s->agg.stepper = uint32_t(s->c->step_kind);
   s->agg_ms = 0.f;
+  s->call_encode_ms = 0.f;
 }
 
 // one window's scan (the context's stats) added to the call's
@@ -1879,6 +1915,7 @@ static void win_stats_add(dgrep_stream* s, uint64_t n) {
 static void win_stats_end(dgrep_stream* s) {
   s->c->stats = s->agg;
   s->c->last_ms = s->agg_ms;
+  if (s->parts) s->c->last_encode_ms = s->call_encode_ms;
 }
 
 // buf[b] holds at least `need` bytes (and the padding the kernels' aligned
@@ -2063,6 +2100,83 @@ static int win_walk(dgrep_stream* s, const uint8_t* d, uint64_t m, bool want_ver
   return DGREP_OK;
 }
 
+// A partition stream's window: the scan's records (the context's result arrays,
+// in the window's coordinates) encoded from the window buffer d[0 : n) into
+// d_enc, and the bytes appended to the call's rows. The buffer is still the
+// stream's: the caller records ev_free behind this.
+static int win_encode(dgrep_stream* s, const uint8_t* d, uint64_t n, uint64_t count) {
+  dgrep_ctx* c = s->c;
+  if (count >= (uint64_t(1) << 32)) {
+    c->err = "partition stream: 2^32 or more matching lines in one window";
+    return DGREP_E_UNSUPPORTED;
+  }
+  int rc;
+  const uint32_t R = s->nreduce;
+  WindowEncodeArgs a;
+  a.e.data = d;
+  a.e.n = n;
+  a.e.line_no = c->d_res_line;
+  a.e.start = c->d_res_start;
+  a.e.len = c->d_res_len;
+  a.e.count = count;
+  a.e.fname_json = s->d_fname;
+  a.e.fname_json_len = s->fname_json_len;
+  a.e.key_hash0 = s->key_hash0;
+  a.e.nreduce = R;
+  a.line_base = s->line_base;
+  a.long_value = c->long_value ? c->long_value : kLongValueDefault;
+  size_t need = 0;
+  HIPCHK(encode_window_partitions(a, nullptr, &need, nullptr, 0, nullptr, c->stream));
+  if ((rc = grow(c, &s->d_pscratch, &s->pscratch_cap, need)) != DGREP_OK) return rc;
+  uint64_t total = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    size_t have = s->pscratch_cap;
+    HIPCHK(hipEventRecord(s->ev_e0, c->stream));
+    HIPCHK(encode_window_partitions(a, s->d_pscratch, &have, s->d_enc, s->enc_cap, s->d_pbounds, c->stream));
+    HIPCHK(hipEventRecord(s->ev_e1, c->stream));
+    HIPCHK(hipMemcpyAsync(s->h_pbounds.data(), s->d_pbounds, s->h_pbounds.size() * 8, hipMemcpyDeviceToHost,
+                          c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, s->ev_e0, s->ev_e1));
+    s->call_encode_ms += ms;
+    s->encode_ms += ms;
+    total = s->h_pbounds[2 * size_t(R)];
+    if (total <= s->enc_cap) break;
+    if (attempt == 1) {
+      c->err = "partition stream: the window's encoded size changed between two passes";
+      return DGREP_E_HIP;
+    }
+    // the one buffer of encoded bytes the device holds: this window's, with a sixteenth to spare
+    if ((rc = grow(c, &s->d_enc, &s->enc_cap, total + total / 16)) != DGREP_OK) return rc;
+  }
+  if (s->cell_bytes + total > s->h_cells_cap) {
+    const uint64_t cap = std::max<uint64_t>(s->cell_bytes + total, 2 * s->h_cells_cap);
+    uint8_t* p = static_cast<uint8_t*>(realloc(s->h_cells, cap));
+    if (!p) return DGREP_E_NOMEM;
+    s->h_cells = p;
+    s->h_cells_cap = cap;
+  }
+  HIPCHK(hipMemcpyAsync(s->h_cells + s->cell_bytes, s->d_enc, total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  // the window's bytes are partition-major and contiguous: a cell ends where the next one begins
+  if (s->cell_off.empty()) s->cell_off.push_back(0);
+  uint64_t at = s->cell_bytes;
+  for (uint32_t p = 0; p < R; ++p) {
+    at += s->h_pbounds[R + p] - s->h_pbounds[p];
+    s->cell_off.push_back(at);
+  }
+  if (at != s->cell_bytes + total) {
+    c->err = "partition stream: the partitions' ranges do not add up to the window's bytes";
+    return DGREP_E_HIP;
+  }
+  s->cell_bytes = at;
+  ++s->rows;
+  s->out_bytes += total;
+  s->long_values += s->h_pbounds[2 * size_t(R) + 1];
+  return DGREP_OK;
+}
+
 // One window's completed lines d[0 : n) (16-byte aligned; n may be 0, the one
 // empty line): scan, then the records rebased and appended to the call's, then
 // their bytes gathered. `splice` (a bounded stream that carries a line): the
@@ -2108,6 +2222,7 @@ static int win_scan(dgrep_stream* s, const uint8_t* d, uint64_t n, bool splice =
     return DGREP_OK;  // a bounded stream returns no values
   }
   if (count == 0) return DGREP_OK;
+  if (s->parts) return win_encode(s, d, n, count);
   if ((rc = win_acc_reserve(s, s->nrec + count)) != DGREP_OK) return rc;
   HIPCHK(window_rebase_append(c->d_res_line, c->d_res_start, c->d_res_len, count, s->line_base, s->byte_base,
                               s->d_line + s->nrec, s->d_start + s->nrec, s->d_len + s->nrec, c->num_cus, c->stream));
@@ -2371,14 +2486,16 @@ extern "C" void dgrep_stream_close(dgrep_stream* s) {
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   void* bufs[] = {s->buf[0], s->buf[1], s->d_cut, s->d_line, s->d_start, s->d_len, s->d_voff, s->d_values, s->d_gscratch,
-                  s->d_carry, s->d_pairs};
+                  s->d_carry, s->d_pairs, s->d_fname, s->d_enc, s->d_pscratch, s->d_pbounds};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (s->h_cut) (void)hipHostFree(s->h_cut);
   if (s->h_verdict) (void)hipHostFree(s->h_verdict);
-  for (hipEvent_t e : {s->ev_c0, s->ev_c1, s->ev_free[0], s->ev_free[1], s->ev_in, s->ev_w0, s->ev_w1, s->ev_v})
+  for (hipEvent_t e : {s->ev_c0, s->ev_c1, s->ev_free[0], s->ev_free[1], s->ev_in, s->ev_w0, s->ev_w1, s->ev_v,
+                       s->ev_e0, s->ev_e1})
     if (e) (void)hipEventDestroy(e);
   free(s->h_values);
+  free(s->h_cells);
   delete s;
 }
 
@@ -2427,6 +2544,12 @@ extern "C" int dgrep_stream_open(dgrep_ctx* c, size_t window_bytes, uint32_t fla
   return rc;
 }
 
+static const char kWantParts[] =
+    "this is a partition stream (dgrep_stream_open_partitions): use dgrep_stream_feed_partitions / "
+    "dgrep_stream_finish_partitions";
+static const char kWantRecords[] =
+    "this is a record stream (dgrep_stream_open): the _partitions calls need dgrep_stream_open_partitions";
+
 // The checks every stream call makes before it touches the GPU.
 static int win_enter(dgrep_stream* s, bool feeding) {
   dgrep_ctx* c = s->c;
@@ -2459,6 +2582,7 @@ extern "C" int dgrep_stream_feed(dgrep_stream* s, const uint8_t* data, size_t n,
   if (out) memset(out, 0, sizeof *out);
   if (!s || !out || (n && !data)) return DGREP_E_INVALID;
   dgrep_ctx* c = s->c;
+  if (s->parts) { c->err = kWantParts; return DGREP_E_INVALID; }
   int rc;
   if ((rc = win_enter(s, true)) != DGREP_OK) return rc;
   win_stats_begin(s);
@@ -2477,6 +2601,7 @@ extern "C" int dgrep_stream_finish(dgrep_stream* s, dgrep_stream_result* out) {
   if (out) memset(out, 0, sizeof *out);
   if (!s || !out) return DGREP_E_INVALID;
   dgrep_ctx* c = s->c;
+  if (s->parts) { c->err = kWantParts; return DGREP_E_INVALID; }
   int rc;
   if ((rc = win_enter(s, false)) != DGREP_OK) return rc;
   win_stats_begin(s);
@@ -2571,6 +2696,164 @@ static int scan_windowed_flags(dgrep_ctx* c, const uint8_t* data, size_t n, size
   out->start = r.start;
   out->len = r.len;
   return DGREP_OK;
+}
+
+// ---- the windowed map task: a stream that returns partition cells ------------
+// The call's rows to the caller, malloc'd; the stream starts its next call's
+// result empty.
+static int win_collect_parts(dgrep_stream* s, dgrep_batch_partitions* out) {
+  const uint64_t ncell = s->cell_off.empty() ? 0 : s->cell_off.size() - 1;
+  out->nreduce = s->nreduce;
+  out->nsplits = ncell / s->nreduce;
+  out->cell_off = static_cast<uint64_t*>(calloc(ncell + 1, 8));
+  if (!out->cell_off) return DGREP_E_NOMEM;
+  if (ncell) memcpy(out->cell_off, s->cell_off.data(), (ncell + 1) * 8);
+  out->total = s->cell_bytes;
+  if (s->cell_bytes) {
+    out->bytes = s->h_cells;
+    s->h_cells = nullptr;
+    s->h_cells_cap = 0;
+  }
+  s->cell_off.clear();
+  s->cell_bytes = 0;
+  return DGREP_OK;
+}
+
+// the argument checks of the partition forms that need no GPU; the message is set
+static int parts_args_ok(dgrep_ctx* c, size_t window_bytes, const char* filename, size_t fn, uint32_t nreduce) {
+  if (!win_window_ok(window_bytes)) {
+    c->err = "window_bytes must be a multiple of 4096 in [4096, 2^40]";
+    return DGREP_E_INVALID;
+  }
+  if (fn && !filename) { c->err = "filename is NULL with fn != 0"; return DGREP_E_INVALID; }
+  if (nreduce == 0 || nreduce > 65535) { c->err = "nreduce must be 1..65535"; return DGREP_E_INVALID; }
+  if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
+  return DGREP_OK;
+}
+
+static int win_open_parts(dgrep_ctx* c, size_t window_bytes, const char* filename, size_t fn, uint32_t nreduce,
+                          dgrep_stream** out) {
+  int rc = win_open(c, window_bytes, 0, out);
+  if (rc != DGREP_OK) return rc;
+  dgrep_stream* s = *out;
+  s->parts = true;
+  s->nreduce = nreduce;
+  const uint8_t* fname = reinterpret_cast<const uint8_t*>(filename);
+  const uint64_t fj = json_escape_host(fname, fn, nullptr);
+  if (fj >= (uint64_t(1) << 31)) { c->err = "filename too long"; return DGREP_E_INVALID; }
+  std::vector<uint8_t> fjson(fj + 1);
+  json_escape_host(fname, fn, fjson.data());
+  s->fname_json_len = uint32_t(fj);
+  s->key_hash0 = key_prefix_hash(fname, fn);
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->d_fname), fj + 1));
+  HIPCHK(hipMemcpy(s->d_fname, fjson.data(), fj + 1, hipMemcpyHostToDevice));
+  s->h_pbounds.assign(2 * size_t(nreduce) + 2, 0);
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->d_pbounds), s->h_pbounds.size() * 8));
+  HIPCHK(hipEventCreate(&s->ev_e0));
+  HIPCHK(hipEventCreate(&s->ev_e1));
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_stream_open_partitions(dgrep_ctx* c, size_t window_bytes, const char* filename, size_t fn,
+                                            uint32_t nreduce, dgrep_stream** out) {
+  if (out) *out = nullptr;
+  if (!c || !out) return DGREP_E_INVALID;
+  int rc;
+  if ((rc = parts_args_ok(c, window_bytes, filename, fn, nreduce)) != DGREP_OK) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  rc = win_open_parts(c, window_bytes, filename, fn, nreduce, out);
+  if (rc != DGREP_OK) {
+    const std::string msg = c->err;
+    dgrep_stream_close(*out);
+    c->err = msg;
+    *out = nullptr;
+  }
+  return rc;
+}
+
+// an empty result: no row, the single offset 0
+static int parts_empty(uint32_t nreduce, dgrep_batch_partitions* out) {
+  out->nreduce = nreduce;
+  return (out->cell_off = static_cast<uint64_t*>(calloc(1, 8))) ? DGREP_OK : DGREP_E_NOMEM;
+}
+
+extern "C" int dgrep_stream_feed_partitions(dgrep_stream* s, const uint8_t* data, size_t n,
+                                            dgrep_batch_partitions* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!s || !out || (n && !data)) return DGREP_E_INVALID;
+  dgrep_ctx* c = s->c;
+  if (!s->parts) { c->err = kWantRecords; return DGREP_E_INVALID; }
+  int rc;
+  if ((rc = win_enter(s, true)) != DGREP_OK) return rc;
+  win_stats_begin(s);
+  if (n && !(c->flags & DGREP_DFA_MATCH_NONE)) {
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = win_fail(s, win_feed(s, data, n))) != DGREP_OK) return rc;
+    if ((rc = win_fail(s, win_collect_parts(s, out))) != DGREP_OK) return rc;
+  } else if ((rc = parts_empty(s->nreduce, out)) != DGREP_OK) {
+    return rc;
+  }
+  win_stats_end(s);
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_stream_finish_partitions(dgrep_stream* s, dgrep_batch_partitions* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!s || !out) return DGREP_E_INVALID;
+  dgrep_ctx* c = s->c;
+  if (!s->parts) { c->err = kWantRecords; return DGREP_E_INVALID; }
+  int rc;
+  if ((rc = win_enter(s, false)) != DGREP_OK) return rc;
+  win_stats_begin(s);
+  if (!(c->flags & DGREP_DFA_MATCH_NONE)) {
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = win_fail(s, win_finish(s))) != DGREP_OK) return rc;
+    if ((rc = win_fail(s, win_collect_parts(s, out))) != DGREP_OK) return rc;
+  } else {
+    s->finished = true;
+    if ((rc = parts_empty(s->nreduce, out)) != DGREP_OK) return rc;
+  }
+  win_stats_end(s);
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_stream_partition_stats(dgrep_stream* s, uint64_t* rows, uint64_t* out_bytes,
+                                            uint64_t* long_values, uint64_t* enc_device_bytes, float* encode_ms) {
+  if (!s) return DGREP_E_INVALID;
+  if (rows) *rows = s->rows;
+  if (out_bytes) *out_bytes = s->out_bytes;
+  if (long_values) *long_values = s->long_values;
+  if (enc_device_bytes) *enc_device_bytes = s->enc_cap;
+  if (encode_ms) *encode_ms = s->encode_ms;
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_map_partitions_windowed(dgrep_ctx* c, const uint8_t* data, size_t n, size_t window_bytes,
+                                             const char* filename, size_t fn, uint32_t nreduce,
+                                             dgrep_batch_partitions* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!c || !out || (n && !data)) return DGREP_E_INVALID;
+  int rc;
+  if ((rc = parts_args_ok(c, window_bytes, filename, fn, nreduce)) != DGREP_OK) return rc;
+  if (c->flags & DGREP_DFA_MATCH_NONE) {
+    c->stats = dgrep_scan_stats{};
+    c->stats.stepper = uint32_t(c->step_kind);
+    c->last_ms = c->last_encode_ms = 0.f;
+    return parts_empty(nreduce, out);
+  }
+  HIPCHK(hipSetDevice(c->device));
+  dgrep_stream* s = nullptr;
+  rc = win_open_parts(c, window_bytes, filename, fn, nreduce, &s);
+  win_stats_begin(s);
+  if (rc == DGREP_OK && n) rc = win_fail(s, win_feed(s, data, n));
+  if (rc == DGREP_OK) rc = win_fail(s, win_finish(s));  // at most one more row, behind the feed's
+  if (rc == DGREP_OK) rc = win_fail(s, win_collect_parts(s, out));
+  if (rc == DGREP_OK) win_stats_end(s);
+  const std::string msg = c->err;
+  dgrep_stream_close(s);  // the context holds no stream when the call returns
+  c->err = msg;
+  if (rc != DGREP_OK) dgrep_batch_partitions_free(out);
+  return rc;
 }
 
 // ---- partition + intermediate writer (map_reduce/worker.go:13-17,78-109) ----

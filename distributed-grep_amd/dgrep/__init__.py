@@ -64,7 +64,13 @@ EXPORTS = (
     "dgrep_scan_windowed", "dgrep_stream_open", "dgrep_stream_feed", "dgrep_stream_finish",
     "dgrep_stream_result_free", "dgrep_stream_close", "dgrep_stream_stats",
     "dgrep_scan_bounded", "dgrep_stream_carry_stats",
+    "dgrep_stream_open_partitions", "dgrep_stream_feed_partitions", "dgrep_stream_finish_partitions",
+    "dgrep_map_partitions_windowed", "dgrep_stream_partition_stats", "dgrep_set_long_value",
 )
+# csrc/kernels/encode_window.h: a long escaped value is cut into chunks of this
+# many bytes, one workgroup each; the default of set_long_value
+LONG_CHUNK = 16384
+LONG_VALUE_DEFAULT = 256
 STREAM_VALUES = 1
 STREAM_BOUNDED = 2
 COMM_ID_BYTES = 128
@@ -279,6 +285,22 @@ def lib() -> ctypes.CDLL:
             L.dgrep_stream_carry_stats.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64),
                                                    ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_float)]
             L.dgrep_stream_carry_stats.restype = i
+            L.dgrep_stream_open_partitions.argtypes = [vp, sz, ctypes.c_char_p, sz, ctypes.c_uint32,
+                                                       ctypes.POINTER(vp)]
+            L.dgrep_stream_open_partitions.restype = i
+            L.dgrep_stream_feed_partitions.argtypes = [vp, vp, sz, ctypes.POINTER(_BatchPartitions)]
+            L.dgrep_stream_feed_partitions.restype = i
+            L.dgrep_stream_finish_partitions.argtypes = [vp, ctypes.POINTER(_BatchPartitions)]
+            L.dgrep_stream_finish_partitions.restype = i
+            L.dgrep_map_partitions_windowed.argtypes = [vp, vp, sz, sz, ctypes.c_char_p, sz, ctypes.c_uint32,
+                                                        ctypes.POINTER(_BatchPartitions)]
+            L.dgrep_map_partitions_windowed.restype = i
+            L.dgrep_stream_partition_stats.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                                       ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                                       ctypes.POINTER(ctypes.c_float)]
+            L.dgrep_stream_partition_stats.restype = i
+            L.dgrep_set_long_value.argtypes = [vp, ctypes.c_uint32]
+            L.dgrep_set_long_value.restype = i
             _lib = L
     return _lib
 
@@ -536,6 +558,32 @@ class Context:
         finally:
             self._L.dgrep_partitions_free(ctypes.byref(res))
 
+    def set_long_value(self, n: int = 0):
+        """Testing/tuning: the value length from which an escaped value takes the
+        window encoder's parallel path (dgrep_set_long_value; 0 = the default,
+        else a multiple of 64 in [256, 2^30]). Only the windowed writer reads it."""
+        self._check(self._L.dgrep_set_long_value(self._h, n))
+
+    def map_partitions_windowed(self, filename, contents, nreduce: int, window: int) -> List[bytes]:
+        """map_partitions() with the split never resident as a whole
+        (dgrep_map_partitions_windowed): element p is the byte content of
+        mr-<task>-<p>, the rows of the windowed result joined per partition."""
+        if isinstance(contents, str):
+            contents = contents.encode("utf-8", "surrogateescape")
+        fname = filename.encode("utf-8", "surrogateescape") if isinstance(filename, str) else bytes(filename)
+        buf = np.frombuffer(contents, dtype=np.uint8) if len(contents) else np.zeros(1, np.uint8)
+        res = _BatchPartitions()
+        self._check(self._L.dgrep_map_partitions_windowed(self._h, ctypes.c_void_p(buf.ctypes.data), len(contents),
+                                                          window, fname, len(fname), nreduce, ctypes.byref(res)))
+        rows = _take_rows(self._L, res)
+        return [b"".join(r[p] for r in rows) for p in range(nreduce)]
+
+    def partition_stream(self, window: int, filename, nreduce: int) -> "PartitionStream":
+        """A stream that returns partition cells (dgrep_stream_open_partitions):
+        feed it a split piece by piece, append cell [w][p] to mr-<task>-<p>.
+        Close it before the context."""
+        return PartitionStream(self, window, filename, nreduce)
+
     def encode_device(self, d_data: int, n: int, d_line: int, d_start: int, d_len: int, count: int, filename,
                       nreduce: int, d_out: int, out_cap: int):
         """dgrep_encode_device: returns (begin[], end[], total)."""
@@ -780,6 +828,64 @@ class Stream:
             pass
 
 
+def _take_rows(L, res: "_BatchPartitions") -> List[List[bytes]]:
+    """rows x partitions of a windowed partition result; frees it"""
+    try:
+        k, R = int(res.nsplits), int(res.nreduce)
+        if k == 0:
+            return []
+        raw = ctypes.string_at(res.bytes, res.total) if res.total else b""
+        off = np.ctypeslib.as_array(res.cell_off, shape=(k * R + 1,)).tolist()
+        return [[raw[off[w * R + p]:off[w * R + p + 1]] for p in range(R)] for w in range(k)]
+    finally:
+        L.dgrep_batch_partitions_free(ctypes.byref(res))
+
+
+class PartitionStream(Stream):
+    """dgrep_stream_*_partitions: a split fed in pieces of any length, returned
+    as the bytes of its map task's intermediate files. feed(piece) and finish()
+    return rows x partitions: one row per window of the call that completed a
+    matching line, element [w][p] = the bytes that window adds to
+    mr-<task>-<p>. Joined per partition over all calls they are
+    Context.map_partitions of the whole split."""
+
+    def __init__(self, ctx: "Context", window: int, filename, nreduce: int):
+        self._L = lib()
+        self.ctx = ctx
+        self.values = self.bounded = False
+        self.nreduce = nreduce
+        fname = filename.encode("utf-8", "surrogateescape") if isinstance(filename, str) else bytes(filename)
+        h = ctypes.c_void_p()
+        self._h = h
+        ctx._check(self._L.dgrep_stream_open_partitions(ctx._h, window, fname, len(fname), nreduce, ctypes.byref(h)))
+
+    def feed(self, piece) -> List[List[bytes]]:
+        piece = piece.encode("utf-8", "surrogateescape") if isinstance(piece, str) else piece
+        buf = np.frombuffer(piece, dtype=np.uint8) if len(piece) else np.zeros(1, np.uint8)
+        res = _BatchPartitions()
+        self.ctx._check(self._L.dgrep_stream_feed_partitions(self._h, ctypes.c_void_p(buf.ctypes.data), len(piece),
+                                                             ctypes.byref(res)))
+        return _take_rows(self._L, res)
+
+    def finish(self) -> List[List[bytes]]:
+        res = _BatchPartitions()
+        self.ctx._check(self._L.dgrep_stream_finish_partitions(self._h, ctypes.byref(res)))
+        return _take_rows(self._L, res)
+
+    def stats(self) -> dict:
+        """Stream.stats() plus dgrep_stream_partition_stats: rows returned, their
+        bytes, values the long-value path took, the device buffer of encoded
+        bytes now (one window's), the encoder's device ms."""
+        d = Stream.stats(self)
+        r, b, lv, e, ms = (ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(),
+                           ctypes.c_float())
+        self.ctx._check(self._L.dgrep_stream_partition_stats(self._h, ctypes.byref(r), ctypes.byref(b),
+                                                             ctypes.byref(lv), ctypes.byref(e), ctypes.byref(ms)))
+        d.update(rows=int(r.value), out_bytes=int(b.value), long_values=int(lv.value),
+                 enc_device_bytes=int(e.value), encode_ms=float(ms.value))
+        return d
+
+
 def build_info() -> str:
     """dgrep_build_info(): "head=<commit>[-dirty] arch=gfx950 hipflags=..."."""
     return lib().dgrep_build_info().decode()
@@ -956,6 +1062,24 @@ def MapStream(filename: str, pieces, window: int = 64 << 20) -> List[KeyValue]:
             take(st.feed(piece))
         take(st.finish())
     return [KeyValue(format_key(filename, n), v.decode("utf-8", "surrogateescape") if text else v) for n, v in kva]
+
+
+def MapPartitionsStream(filename, pieces, nreduce: int, window: int = 64 << 20) -> List[bytes]:
+    """The map task of a worker that reads its file piece by piece, with the set
+    pattern (dgrep_stream_*_partitions): element p is the byte content of
+    mr-<task>-<p>, equal to Context.map_partitions(filename, b"".join(pieces),
+    nreduce). Every piece is fed as it comes; the key formatting, ihash, JSON
+    escaping and partitioning happen on the device, window by window."""
+    parts = [[] for _ in range(nreduce)]
+    with _context().partition_stream(window, filename, nreduce) as st:
+        def take(rows):
+            for row in rows:
+                for p, cell in enumerate(row):
+                    parts[p].append(cell)
+        for piece in pieces:
+            take(st.feed(piece))
+        take(st.finish())
+    return [b"".join(x) for x in parts]
 
 
 def MapBatch(files: Sequence[Tuple[str, object]]) -> List[List[KeyValue]]:

@@ -436,6 +436,73 @@ int dgrep_map_partitions_batch(dgrep_ctx* ctx, const uint8_t* const* data, const
                                dgrep_batch_partitions* out);
 void dgrep_batch_partitions_free(dgrep_batch_partitions* p);
 
+/* ---- the windowed map task: a streamed split's intermediate files -------------
+ * A partition stream is a windowed stream (above) that returns encoded
+ * partition pieces instead of records: the worker that streams its file gets
+ * the bytes to append to mr-<task>-<p>, with the key formatting, ihash, JSON
+ * escaping and partitioning done on the device, window by window. It has its
+ * own open call (no flag bit of dgrep_stream_open) and no bounded form: a
+ * folded line's bytes are gone, and its value could not be written.
+ *
+ * Result: dgrep_batch_partitions with ROWS in place of splits, freed with
+ * dgrep_batch_partitions_free. A row is one window of the call that completed
+ * at least one matching line, in stream order; nsplits is the number of rows;
+ * cell c = row * nreduce + p holds the bytes that window adds to
+ * mr-<task>-<p>. cell_off has nsplits * nreduce + 1 entries; with no row it is
+ * the single entry 0, total is 0 and bytes is NULL.
+ *
+ * Contract: fix a partition p, take all feeds in order and then the finish, and
+ * concatenate cells (0,p), (1,p), ... of each result: that is bit for bit
+ * partition p of dgrep_map_partitions(whole split, filename, nreduce), however
+ * the stream is cut into feeds and whatever the window. The line numbers in the
+ * keys are the stream's own.
+ *
+ * The layout needs no merge and feeds the reduce directly: it is
+ * dgrep_reduce_batch_device's segment convention (segment g belongs to
+ * partition g % nparts), so the cells of a big file are batch-reduce input
+ * with seg_off = cell_off and nparts = nreduce.
+ *
+ * Footprint: the two window buffers, the encoder's per-record scratch, and ONE
+ * window's encoded bytes (dgrep_stream_partition_stats, enc_device_bytes). A
+ * partition stream keeps no record arrays. dgrep_last_scan_stats and
+ * dgrep_last_kernel_ms behave as for any windowed call; dgrep_last_encode_ms
+ * is the sum over the call's windows.
+ *
+ * A value that needs escaping and has at least `long value` bytes
+ * (dgrep_set_long_value) is escaped by many workgroups at once, not by one
+ * lane as in dgrep_map_partitions: minified JSON, binaries and logs with
+ * embedded blobs are what windows are for.
+ *
+ * DGREP_E_INVALID before any GPU call, result zeroed: the checks of
+ * dgrep_stream_open / dgrep_stream_feed; filename == NULL with fn != 0; nreduce
+ * outside 1..65535. DGREP_E_INVALID with a message naming the mismatch:
+ * dgrep_stream_feed / dgrep_stream_finish on a partition stream, the
+ * _partitions calls on a record stream. No DFA loaded: DGREP_E_NO_DFA. A
+ * DGREP_DFA_MATCH_NONE pattern gives empty results and copies nothing.
+ * DGREP_E_UNSUPPORTED (with a message): 2^32 or more matching lines in one
+ * window. A load on the context mid-stream, a feed after finish and a sticky
+ * HIP error behave as in record streams. DGREP_DFA_PARTIAL patterns work. */
+int dgrep_stream_open_partitions(dgrep_ctx* ctx, size_t window_bytes, const char* filename, size_t fn,
+                                 uint32_t nreduce, dgrep_stream** stream);
+int dgrep_stream_feed_partitions(dgrep_stream* stream, const uint8_t* data, size_t n, dgrep_batch_partitions* out);
+int dgrep_stream_finish_partitions(dgrep_stream* stream, dgrep_batch_partitions* out);
+/* open, feed(data, n), finish, both results joined into one (the finish
+ * contributes at most one more row); the context holds no stream afterwards. */
+int dgrep_map_partitions_windowed(dgrep_ctx* ctx, const uint8_t* data, size_t n, size_t window_bytes,
+                                  const char* filename, size_t fn, uint32_t nreduce, dgrep_batch_partitions* out);
+/* Over the stream's life: rows returned, their bytes, values the long-value
+ * path took, the device buffer of encoded bytes now (one window's), the
+ * encoder's device ms (HIP events). All 0 on a record stream. Any pointer may
+ * be NULL. */
+int dgrep_stream_partition_stats(dgrep_stream* stream, uint64_t* rows, uint64_t* out_bytes, uint64_t* long_values,
+                                 uint64_t* enc_device_bytes, float* encode_ms);
+/* Tests / tuning, like dgrep_set_lane_chunk: the value length at and above
+ * which an escaped value takes the window encoder's parallel path. 0 = the
+ * built-in default; else a multiple of 64 in [256, 2^30]; anything else is
+ * DGREP_E_INVALID and leaves the setting unchanged. Affects only the window
+ * encoder. */
+int dgrep_set_long_value(dgrep_ctx* ctx, uint32_t bytes);
+
 /* Device form: the records exactly as dgrep_scan_batch_device returned them
  * over the same packed buffer (line_no and start relative to the record's
  * split, d_split filled; `count` of them) -> every cell's lines in d_out
