@@ -1,6 +1,8 @@
-// encode_common.h — what the single-split writer (encode.hip) and the batch
-// writer (encode_batch.hip) share: Go's JSON string escaping, the key hash
-// step, decimal digits, and the SWAR / realigned-copy helpers.
+// encode_common.h — the byte-level rules of the three partition writers
+// (encode.hip, encode_batch.hip, encode_window.hip): Go's JSON string escaping,
+// the key hash step, decimal digits, and the SWAR / realigned-copy helpers. It
+// compiles as plain C++ too (tests/escape_c). The pipeline that the resident
+// and the batch writer build on these is encode_pipeline.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
