@@ -25,11 +25,13 @@
 #include "../kernels/encode.h"
 #include "../kernels/encode_batch.h"
 #include "../kernels/encode_window.h"
+#include "../kernels/job_arena.h"
 #include "../kernels/reduce.h"
 #include "../kernels/reduce_batch.h"
 #include "../kernels/scan_common.h"
 #include "../kernels/synth.h"
 #include "../kernels/window.h"
+#include "job_plan.h"
 #include "pack_pieces.h"
 
 // DFAs of at most this many states use the Sheng stepper (8 = its limit; 0
@@ -251,6 +253,9 @@ struct dgrep_ctx {
   uint64_t rb_off_cap = 0;
   hipEvent_t evr0 = nullptr, evr1 = nullptr;
   float last_reduce_ms = 0.f;
+  // the host pack buffer of the last closed job (dgrep_job_*): the next job takes it over, touched pages and all
+  uint8_t* h_job_pack = nullptr;
+  size_t h_job_pack_cap = 0;
 
   // The blob's plain DFA, kept on the host for a bounded stream's carry walk
   // (kernels/carry.h): uploaded the first time a stream folds, so a context
@@ -602,6 +607,7 @@ extern "C" void dgrep_close(dgrep_ctx* c) {
   for (hipEvent_t e : {c->evb0, c->evb1, c->evb2, c->evb3, c->evr0, c->evr1})
     if (e) (void)hipEventDestroy(e);
   if (c->h_bat_flag) (void)hipHostFree(c->h_bat_flag);
+  free(c->h_job_pack);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }
@@ -1798,6 +1804,11 @@ extern "C" int dgrep_last_batch_ms(dgrep_ctx* c, float* newline_ms, float* rebas
 // scan_resident as they are and their records rebased by the stream's running
 // (byte_base, line_base), so the concatenated records are those of dgrep_scan
 // on the concatenated bytes, for every cut.
+struct dgrep_job;
+// a job's flush or window: `total` encoded bytes at d_src, their cell ends at d_end, into the job's arena
+static int job_append_rows(dgrep_job* j, const uint8_t* d_src, uint64_t total, const uint64_t* d_end, uint64_t nend,
+                           bool running_max, uint64_t rows, uint64_t lines);
+
 struct dgrep_stream {
   dgrep_ctx* c = nullptr;
   size_t window = 0;
@@ -1875,6 +1886,10 @@ struct dgrep_stream {
   // dgrep_stream_partition_stats
   uint64_t rows = 0, out_bytes = 0, long_values = 0;
   float encode_ms = 0.f;
+  // the window route of a job (dgrep_job_*): the rows go to the job's device
+  // arena and their boundaries to its segment table, nothing to the host
+  dgrep_job* job = nullptr;
+  uint64_t fname_cap = 0;
 };
 
 static uint32_t* carry_state(dgrep_stream* s) { return reinterpret_cast<uint32_t*>(s->d_carry + 2); }
@@ -2134,8 +2149,12 @@ static int win_encode(dgrep_stream* s, const uint8_t* d, uint64_t n, uint64_t co
     HIPCHK(hipEventRecord(s->ev_e0, c->stream));
     HIPCHK(encode_window_partitions(a, s->d_pscratch, &have, s->d_enc, s->enc_cap, s->d_pbounds, c->stream));
     HIPCHK(hipEventRecord(s->ev_e1, c->stream));
-    HIPCHK(hipMemcpyAsync(s->h_pbounds.data(), s->d_pbounds, s->h_pbounds.size() * 8, hipMemcpyDeviceToHost,
-                          c->stream));
+    if (s->job)  // the totals only: the offsets stay on the device
+      HIPCHK(hipMemcpyAsync(s->h_pbounds.data() + 2 * size_t(R), s->d_pbounds + 2 * size_t(R), 16,
+                            hipMemcpyDeviceToHost, c->stream));
+    else
+      HIPCHK(hipMemcpyAsync(s->h_pbounds.data(), s->d_pbounds, s->h_pbounds.size() * 8, hipMemcpyDeviceToHost,
+                            c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, s->ev_e0, s->ev_e1));
@@ -2148,7 +2167,17 @@ static int win_encode(dgrep_stream* s, const uint8_t* d, uint64_t n, uint64_t co
       return DGREP_E_HIP;
     }
     // the one buffer of encoded bytes the device holds: this window's, with a sixteenth to spare
-    if ((rc = grow(c, &s->d_enc, &s->enc_cap, total + total / 16)) != DGREP_OK) return rc;
+    // (a job's append kernel reads whole 16-byte vectors)
+    const uint64_t want = s->job ? (total + total / 16 + 15) & ~uint64_t(15) : total + total / 16;
+    if ((rc = grow(c, &s->d_enc, &s->enc_cap, want)) != DGREP_OK) return rc;
+  }
+  if (s->job) {
+    ++s->rows;
+    s->out_bytes += total;
+    s->long_values += s->h_pbounds[2 * size_t(R) + 1];
+    // the partitions lie in order and back to back, an empty one's range is (0, 0): the running maximum
+    // of their ends are the row's cell boundaries
+    return job_append_rows(s->job, s->d_enc, total, s->d_pbounds + R, R, true, 1, count);
   }
   if (s->cell_bytes + total > s->h_cells_cap) {
     const uint64_t cap = std::max<uint64_t>(s->cell_bytes + total, 2 * s->h_cells_cap);
@@ -3456,6 +3485,459 @@ extern "C" int dgrep_grep_job(dgrep_ctx* c, const uint8_t* const* data, const si
   if ((rc = reduce_batch_owned(c, c->d_enc_out, enc_total, c->d_bat_cells, cells, nreduce, nlines, out)) != DGREP_OK)
     return fail(rc);
   return DGREP_OK;
+}
+
+// ---- the whole job in windows: files of any size (job_plan.h, kernels/job_arena.h)
+// dgrep_grep_job with no input resident as a whole. Files arrive in task order;
+// job_plan.h routes each one: small whole files are packed up to one window and
+// flushed through the batch scan and the batch encode (the pack route), every
+// other file streams through the job's one partition stream (the window
+// route). Either way the encoded cells are appended on the device to the arena
+// and their boundaries to the segment table, and dgrep_job_finish runs the batch
+// reduce over both: segment g belongs to partition g % nreduce, and a
+// partition's segments lie in task order, then line order.
+struct dgrep_job {
+  dgrep_ctx* c = nullptr;
+  JobPlan plan;
+  uint64_t gen = 0;
+  int status = DGREP_OK;  // a failure mid-job: every later call returns it
+  bool finished = false, in_file = false;
+  dgrep_stream* s = nullptr;  // the window route: buffers, scratch and d_enc live as long as the job
+  // the open pack (host): P = f_0 '\n' f_1 ... as job_plan.h lays it out, and its files
+  uint8_t* pack = nullptr;
+  size_t pack_cap = 0;
+  std::vector<size_t> pack_off, pack_len;
+  std::vector<std::string> pack_name;
+  // the arena and the segment table (device); plan.used bytes and plan.nseg + 1 entries are valid
+  uint8_t* d_arena = nullptr;
+  uint64_t arena_cap = 0, arena_growths = 0;
+  uint64_t* d_seg = nullptr;
+  uint64_t seg_cap = 0;
+  hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr;  // the last append
+  bool append_untimed = false;
+  float append_ms = 0.f, reduce_ms = 0.f;
+};
+
+// the last append's device time, once it is known to be done
+static int job_append_ms_take(dgrep_job* j) {
+  dgrep_ctx* c = j->c;
+  if (!j->append_untimed) return DGREP_OK;
+  HIPCHK(hipEventSynchronize(j->ev_a1));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, j->ev_a0, j->ev_a1));
+  j->append_ms += ms;
+  j->append_untimed = false;
+  return DGREP_OK;
+}
+
+// *p holds `need` units of T; the first `keep` survive. Old and new buffer
+// exist together for the one device copy.
+template <class T>
+static int job_grow(dgrep_job* j, T** p, uint64_t* cap, uint64_t need, uint64_t keep, uint64_t initial,
+                    const char* what) {
+  dgrep_ctx* c = j->c;
+  if (*p && *cap >= need) return DGREP_OK;
+  const uint64_t want = job_grow_cap(*p ? *cap : 0, need, initial);
+  T* fresh = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&fresh), want * sizeof(T)) != hipSuccess) {
+    (void)hipGetLastError();
+    c->err = std::string("job ") + what + ": out of device memory (" + std::to_string(want * sizeof(T)) + " bytes)";
+    return DGREP_E_NOMEM;
+  }
+  if (*p) {
+    if (keep) HIPCHK(hipMemcpyAsync(fresh, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));  // the copy, and every append into the old buffer
+    HIPCHK(hipFree(*p));
+  }
+  *p = fresh;
+  *cap = want;
+  return DGREP_OK;
+}
+
+static int job_append_rows(dgrep_job* j, const uint8_t* d_src, uint64_t total, const uint64_t* d_end, uint64_t nend,
+                           bool running_max, uint64_t rows, uint64_t lines) {
+  dgrep_ctx* c = j->c;
+  const uint64_t nseg0 = j->plan.nseg, used0 = j->plan.used;
+  uint64_t at = 0;
+  int limit = 0;
+  if (!job_append(&j->plan, rows, total, lines, &at, &limit)) {
+    c->err = limit == 0 ? "job: 2^32 or more segments (nreduce for every packed file and every window with a match)"
+                        : "job: 2^32 or more matching lines";
+    return DGREP_E_UNSUPPORTED;
+  }
+  int rc;
+  const bool first = j->d_seg == nullptr;
+  const uint64_t had = j->arena_cap;
+  // (the reduce reads whole 16-byte vectors: the capacity is a multiple of 16)
+  if ((rc = job_grow(j, &j->d_arena, &j->arena_cap, (at + total + 15) & ~uint64_t(15), used0, kJobArenaInitial,
+                     "arena")) != DGREP_OK)
+    return rc;
+  if (had && j->arena_cap != had) ++j->arena_growths;
+  if ((rc = job_grow(j, &j->d_seg, &j->seg_cap, j->plan.nseg + 1, nseg0 + 1, kJobSegInitial, "segment table")) !=
+      DGREP_OK)
+    return rc;
+  if (first) HIPCHK(hipMemsetAsync(j->d_seg, 0, 8, c->stream));  // seg_off[0] = 0
+  ArenaAppendArgs a;
+  a.src = d_src;
+  a.total = total;
+  a.arena = j->d_arena;
+  a.used = at;
+  a.src_end = d_end;
+  a.nend = nend;
+  a.running_max = running_max;
+  a.seg = j->d_seg + nseg0 + 1;
+  if ((rc = job_append_ms_take(j)) != DGREP_OK) return rc;
+  HIPCHK(hipEventRecord(j->ev_a0, c->stream));
+  HIPCHK(arena_append(a, c->num_cus, c->stream));
+  HIPCHK(hipEventRecord(j->ev_a1, c->stream));
+  j->append_untimed = true;
+  return DGREP_OK;
+}
+
+// The open pack through one packed ingest, one batch scan and one batch encode;
+// its k * nreduce cells to the arena. A pack without a matching line appends
+// nothing, as a window without one.
+static int job_flush(dgrep_job* j) {
+  dgrep_ctx* c = j->c;
+  uint64_t bytes = 0;
+  const uint64_t k = job_pack_flush(&j->plan, &bytes);
+  if (k == 0 || (c->flags & DGREP_DFA_MATCH_NONE)) return DGREP_OK;  // (no line can match: the plan's tallies only)
+  std::vector<const uint8_t*> data(k);
+  std::vector<const char*> fname(k);
+  std::vector<size_t> fn(k);
+  for (uint64_t i = 0; i < k; ++i) {
+    data[i] = j->pack_len[i] ? j->pack + j->pack_off[i] : nullptr;
+    fname[i] = j->pack_name[i].data();
+    fn[i] = j->pack_name[i].size();
+  }
+  int rc;
+  std::vector<uint8_t> names;
+  if ((rc = build_name_table(c, fname.data(), fn.data(), k, &names)) != DGREP_OK) return rc;
+  uint64_t count = 0;
+  rc = batch_scan_host(c, data.data(), j->pack_len.data(), k, bytes, false, &count);
+  j->pack_off.clear();
+  j->pack_len.clear();
+  j->pack_name.clear();
+  if (rc != DGREP_OK) return rc;
+  win_stats_add(j->s, bytes);
+  if (count >= kJobMaxLines) { c->err = "job: 2^32 or more matching lines in one pack"; return DGREP_E_UNSUPPORTED; }
+  if (count == 0) return DGREP_OK;
+  uint64_t enc_total = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if ((rc = encode_batch_resident(c, c->d_data, bytes, k, c->d_res_line, c->d_res_start, c->d_res_len, c->d_res_split,
+                                    count, names, j->plan.nreduce, c->d_enc_out, c->enc_out_cap, nullptr,
+                                    &enc_total)) != DGREP_OK)
+      return rc;
+    j->s->call_encode_ms += c->last_encode_ms;
+    // (the append kernel reads whole 16-byte vectors)
+    if (enc_total <= c->enc_out_cap && ((enc_total + 15) & ~uint64_t(15)) <= c->enc_out_cap) break;
+    if (attempt == 1) {
+      c->err = "job: the pack's encoded size changed between two passes";
+      return DGREP_E_HIP;
+    }
+    if ((rc = grow(c, &c->d_enc_out, &c->enc_out_cap, (enc_total + enc_total / 16 + 15) & ~uint64_t(15))) != DGREP_OK)
+      return rc;
+  }
+  return job_append_rows(j, c->d_enc_out, enc_total, c->d_bat_cells + 1, k * uint64_t(j->plan.nreduce), false, k, count);
+}
+
+// the window route's next file: the stream's state is reset, its buffers stay
+static int job_file_start(dgrep_job* j, const char* filename, size_t fn) {
+  dgrep_ctx* c = j->c;
+  dgrep_stream* s = j->s;
+  const uint8_t* fname = reinterpret_cast<const uint8_t*>(filename);
+  const uint64_t fj = json_escape_host(fname, fn, nullptr);
+  if (fj >= (uint64_t(1) << 31)) { c->err = "filename too long"; return DGREP_E_INVALID; }
+  std::vector<uint8_t> fjson(fj + 1);
+  json_escape_host(fname, fn, fjson.data());
+  int rc;
+  if ((rc = grow(c, &s->d_fname, &s->fname_cap, fj + 1)) != DGREP_OK) return rc;
+  HIPCHK(hipMemcpy(s->d_fname, fjson.data(), fj + 1, hipMemcpyHostToDevice));
+  s->fname_json_len = uint32_t(fj);
+  s->key_hash0 = key_prefix_hash(fname, fn);
+  s->cur = 0;
+  s->fill = 0;
+  s->byte_base = s->line_base = 0;
+  s->finished = false;
+  return DGREP_OK;
+}
+
+// The checks every job call makes before it touches the GPU.
+static int job_enter(dgrep_job* j, const char* call) {
+  dgrep_ctx* c = j->c;
+  if (j->status != DGREP_OK) return j->status;
+  if (j->finished) {
+    c->err = std::string(call) + " after dgrep_job_finish";
+    return DGREP_E_INVALID;
+  }
+  if (j->gen != c->load_gen) {
+    c->err = "a pattern was loaded while this job was open: its cells would mix two patterns";
+    return DGREP_E_INVALID;
+  }
+  return DGREP_OK;
+}
+
+// a failure mid-job leaves the job unusable; nothing of the caller's is read after the return
+static int job_fail(dgrep_job* j, int rc) {
+  if (rc == DGREP_OK) return rc;
+  dgrep_ctx* c = j->c;
+  const std::string msg = c->err;
+  j->status = rc;
+  if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  (void)hipGetLastError();
+  c->err = msg;
+  return rc;
+}
+
+extern "C" void dgrep_job_close(dgrep_job* j) {
+  if (!j) return;
+  dgrep_ctx* c = j->c;
+  (void)hipSetDevice(c->device);
+  if (j->s) dgrep_stream_close(j->s);  // (waits for both streams)
+  else if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (j->d_arena) (void)hipFree(j->d_arena);
+  if (j->d_seg) (void)hipFree(j->d_seg);
+  if (j->pack && !c->h_job_pack) {  // kept for the context's next job
+    c->h_job_pack = j->pack;
+    c->h_job_pack_cap = j->pack_cap;
+  } else {
+    free(j->pack);
+  }
+  for (hipEvent_t e : {j->ev_a0, j->ev_a1})
+    if (e) (void)hipEventDestroy(e);
+  delete j;
+}
+
+static int job_open(dgrep_ctx* c, size_t window_bytes, uint32_t nreduce, dgrep_job** out) {
+  dgrep_job* j = new dgrep_job();
+  j->c = c;
+  j->plan.window = window_bytes;
+  j->plan.nreduce = nreduce;
+  j->gen = c->load_gen;
+  *out = j;  // kept on failure too: dgrep_job_close frees what was made
+  j->pack = c->h_job_pack;
+  j->pack_cap = c->h_job_pack_cap;
+  c->h_job_pack = nullptr;
+  c->h_job_pack_cap = 0;
+  int rc;
+  if ((rc = win_open(c, window_bytes, 0, &j->s)) != DGREP_OK) return rc;
+  dgrep_stream* s = j->s;
+  s->parts = true;
+  s->nreduce = nreduce;
+  s->job = j;
+  s->h_pbounds.assign(2 * size_t(nreduce) + 2, 0);
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->d_pbounds), s->h_pbounds.size() * 8));
+  for (hipEvent_t* e : {&s->ev_e0, &s->ev_e1, &j->ev_a0, &j->ev_a1}) HIPCHK(hipEventCreate(e));
+  win_stats_begin(s);  // the scan stats and the encode time are summed over the job
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_job_open(dgrep_ctx* c, size_t window_bytes, uint32_t nreduce, dgrep_job** out) {
+  if (out) *out = nullptr;
+  if (!c || !out) return DGREP_E_INVALID;
+  int rc;
+  if ((rc = parts_args_ok(c, window_bytes, nullptr, 0, nreduce)) != DGREP_OK) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  rc = job_open(c, window_bytes, nreduce, out);
+  if (rc != DGREP_OK) {
+    const std::string msg = c->err;
+    dgrep_job_close(*out);
+    c->err = msg;
+    *out = nullptr;
+  }
+  return rc;
+}
+
+// the window route from its first byte: the pack goes first, so the arena stays in task order
+static int job_window_begin(dgrep_job* j, const char* filename, size_t fn, bool flush_first) {
+  int rc;
+  if (flush_first && (rc = job_flush(j)) != DGREP_OK) return rc;
+  return job_file_start(j, filename, fn);
+}
+
+extern "C" int dgrep_job_add(dgrep_job* j, const uint8_t* data, size_t n, const char* filename, size_t fn) {
+  if (!j || (n && !data)) return DGREP_E_INVALID;
+  dgrep_ctx* c = j->c;
+  if (fn && !filename) { c->err = "filename is NULL with fn != 0"; return DGREP_E_INVALID; }
+  int rc;
+  if ((rc = job_enter(j, "dgrep_job_add")) != DGREP_OK) return rc;
+  if (j->in_file) { c->err = "dgrep_job_add inside a file: dgrep_job_file_end comes first"; return DGREP_E_INVALID; }
+  const JobStep step = job_next_file(&j->plan, n, false);
+  if (c->flags & DGREP_DFA_MATCH_NONE) {  // no line can match: the file is routed and counted, nothing is copied
+    if (step.flush_first) (void)job_flush(j);
+    if (step.route == kJobRoutePack) job_pack_push(&j->plan, n);
+    return DGREP_OK;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  if (step.route == kJobRouteWindow) {
+    if ((rc = job_fail(j, job_window_begin(j, filename, fn, step.flush_first))) != DGREP_OK) return rc;
+    if ((rc = job_fail(j, win_feed(j->s, data, n))) != DGREP_OK) return rc;
+    return job_fail(j, win_finish(j->s));
+  }
+  if (step.flush_first && (rc = job_fail(j, job_flush(j))) != DGREP_OK) return rc;
+  // the caller's bytes are borrowed for this call only: the pack keeps a copy
+  const uint64_t off = job_pack_push(&j->plan, n);
+  if (off + n > j->pack_cap) {
+    // geometric up to the window, which no pack exceeds
+    const size_t cap = std::max<size_t>(off + n, std::min<size_t>(std::max<size_t>(2 * j->pack_cap, size_t(1) << 20),
+                                                                   j->plan.window));
+    uint8_t* p = static_cast<uint8_t*>(realloc(j->pack, cap));
+    if (!p) { c->err = "job: out of host memory for the pack"; return job_fail(j, DGREP_E_NOMEM); }
+    j->pack = p;
+    j->pack_cap = cap;
+  }
+  if (off) j->pack[off - 1] = uint8_t('\n');
+  const int T = std::max(1, c->ingest_threads);
+  if (T == 1 || n < (size_t(1) << 20)) {
+    if (n) memcpy(j->pack + off, data, n);
+  } else {  // as the ingest copies a large piece: by its CPU threads
+    std::vector<std::thread> th;
+    const size_t part = ((n + T - 1) / T + 4095) & ~size_t(4095);
+    uint8_t* dst = j->pack + off;
+    for (int t = 0; t < T; ++t) {
+      const size_t a = size_t(t) * part;
+      if (a >= n) break;
+      const size_t m = std::min(part, n - a);
+      th.emplace_back([=] { memcpy(dst + a, data + a, m); });
+    }
+    for (auto& x : th) x.join();
+  }
+  j->pack_off.push_back(off);
+  j->pack_len.push_back(n);
+  j->pack_name.emplace_back(filename ? filename : "", fn);
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_job_file_begin(dgrep_job* j, const char* filename, size_t fn) {
+  if (!j) return DGREP_E_INVALID;
+  dgrep_ctx* c = j->c;
+  if (fn && !filename) { c->err = "filename is NULL with fn != 0"; return DGREP_E_INVALID; }
+  int rc;
+  if ((rc = job_enter(j, "dgrep_job_file_begin")) != DGREP_OK) return rc;
+  if (j->in_file) { c->err = "dgrep_job_file_begin inside a file: dgrep_job_file_end comes first"; return DGREP_E_INVALID; }
+  j->in_file = true;
+  const JobStep step = job_next_file(&j->plan, 0, true);
+  if (c->flags & DGREP_DFA_MATCH_NONE) {
+    if (step.flush_first) (void)job_flush(j);
+    return DGREP_OK;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  return job_fail(j, job_window_begin(j, filename, fn, step.flush_first));
+}
+
+extern "C" int dgrep_job_file_feed(dgrep_job* j, const uint8_t* data, size_t n) {
+  if (!j || (n && !data)) return DGREP_E_INVALID;
+  dgrep_ctx* c = j->c;
+  int rc;
+  if ((rc = job_enter(j, "dgrep_job_file_feed")) != DGREP_OK) return rc;
+  if (!j->in_file) { c->err = "dgrep_job_file_feed without dgrep_job_file_begin"; return DGREP_E_INVALID; }
+  if (n == 0 || (c->flags & DGREP_DFA_MATCH_NONE)) return DGREP_OK;
+  HIPCHK(hipSetDevice(c->device));
+  return job_fail(j, win_feed(j->s, data, n));
+}
+
+extern "C" int dgrep_job_file_end(dgrep_job* j) {
+  if (!j) return DGREP_E_INVALID;
+  dgrep_ctx* c = j->c;
+  int rc;
+  if ((rc = job_enter(j, "dgrep_job_file_end")) != DGREP_OK) return rc;
+  if (!j->in_file) { c->err = "dgrep_job_file_end without dgrep_job_file_begin"; return DGREP_E_INVALID; }
+  j->in_file = false;
+  if (c->flags & DGREP_DFA_MATCH_NONE) return DGREP_OK;
+  HIPCHK(hipSetDevice(c->device));
+  return job_fail(j, win_finish(j->s));
+}
+
+static int job_finish(dgrep_job* j, dgrep_reduce_batch_out* out) {
+  dgrep_ctx* c = j->c;
+  int rc;
+  if ((rc = job_flush(j)) != DGREP_OK) return rc;
+  if ((rc = job_append_ms_take(j)) != DGREP_OK) return rc;
+  win_stats_end(j->s);  // the sums over the job's packs and windows
+  c->last_reduce_ms = 0.f;
+  if (j->plan.lines == 0) return DGREP_OK;  // no matching line: every mr-out-<r> is empty
+  // the table's last entry is the arena's end, or the appends and the plan disagree
+  uint64_t end = 0;
+  HIPCHK(hipMemcpyAsync(&end, j->d_seg + j->plan.nseg, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (end != j->plan.used) {
+    c->err = "dgrep_job_finish: the segment table does not end where the arena does";
+    return DGREP_E_HIP;
+  }
+  uint64_t nlines = 0;
+  if ((rc = reduce_count_host(c, j->d_arena, j->plan.used, &nlines)) != DGREP_OK) return rc;
+  if (nlines != j->plan.lines) {
+    c->err = "dgrep_job_finish: the arena does not hold one line per record";
+    return DGREP_E_INVALID;
+  }
+  rc = reduce_batch_owned(c, j->d_arena, j->plan.used, j->d_seg, j->plan.nseg, j->plan.nreduce, nlines, out);
+  j->reduce_ms = c->last_reduce_ms;
+  return rc;
+}
+
+extern "C" int dgrep_job_finish(dgrep_job* j, dgrep_reduce_batch_out* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!j || !out) return DGREP_E_INVALID;
+  dgrep_ctx* c = j->c;
+  int rc;
+  if ((rc = job_enter(j, "dgrep_job_finish")) != DGREP_OK) return rc;
+  if (j->in_file) { c->err = "dgrep_job_finish inside a file: dgrep_job_file_end comes first"; return DGREP_E_INVALID; }
+  if (!reduce_batch_alloc(out, j->plan.nreduce)) return DGREP_E_NOMEM;
+  HIPCHK(hipSetDevice(c->device));
+  if ((rc = job_fail(j, job_finish(j, out))) != DGREP_OK) {
+    const std::string msg = c->err;
+    dgrep_reduce_batch_free(out);
+    c->err = msg;
+    return rc;
+  }
+  j->finished = true;
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_job_stats_get(dgrep_job* j, dgrep_job_stats* out, size_t out_size) {
+  if (!j || !out || out_size == 0) return DGREP_E_INVALID;
+  dgrep_job_stats st;
+  memset(&st, 0, sizeof st);
+  const dgrep_stream* s = j->s;
+  st.files = j->plan.files;
+  st.packs = j->plan.packs;
+  st.files_packed = j->plan.files_packed;
+  st.files_windowed = j->plan.files_windowed;
+  st.windows = s->windows;
+  st.rows = j->plan.rows;
+  st.segments = j->plan.nseg;
+  st.arena_bytes = j->plan.used;
+  st.arena_device_bytes = j->arena_cap;
+  st.window_device_bytes = s->cap[0] + s->cap[1];
+  st.long_values = s->long_values;
+  st.arena_growths = j->arena_growths;
+  st.scan_ms = s->agg_ms;
+  st.encode_ms = s->call_encode_ms;
+  st.append_ms = j->append_ms;
+  st.reduce_ms = j->reduce_ms;
+  // a shorter (older) caller layout gets its own size; a longer one a zeroed tail
+  const size_t k = std::min(out_size, sizeof st);
+  memcpy(out, &st, k);
+  if (out_size > k) memset(reinterpret_cast<uint8_t*>(out) + k, 0, out_size - k);
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_grep_job_windowed(dgrep_ctx* c, const uint8_t* const* data, const size_t* n,
+                                       const char* const* filename, const size_t* fn, size_t nsplits, uint32_t nreduce,
+                                       size_t window_bytes, dgrep_reduce_batch_out* out) {
+  if (out) memset(out, 0, sizeof *out);
+  if (!c || !out || (nsplits && (!data || !n || !filename || !fn))) return DGREP_E_INVALID;
+  for (size_t i = 0; i < nsplits; ++i)
+    if ((n[i] && !data[i]) || (fn[i] && !filename[i])) return DGREP_E_INVALID;
+  dgrep_job* j = nullptr;
+  int rc = dgrep_job_open(c, window_bytes, nreduce, &j);
+  for (size_t i = 0; rc == DGREP_OK && i < nsplits; ++i) rc = dgrep_job_add(j, data[i], n[i], filename[i], fn[i]);
+  if (rc == DGREP_OK) rc = dgrep_job_finish(j, out);
+  const std::string msg = c->err;
+  dgrep_job_close(j);  // the context holds no job when the call returns
+  c->err = msg;
+  return rc;
 }
 
 extern "C" int dgrep_last_reduce_ms(dgrep_ctx* c, float* ms) {

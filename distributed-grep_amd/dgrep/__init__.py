@@ -66,6 +66,8 @@ EXPORTS = (
     "dgrep_scan_bounded", "dgrep_stream_carry_stats",
     "dgrep_stream_open_partitions", "dgrep_stream_feed_partitions", "dgrep_stream_finish_partitions",
     "dgrep_map_partitions_windowed", "dgrep_stream_partition_stats", "dgrep_set_long_value",
+    "dgrep_job_open", "dgrep_job_add", "dgrep_job_file_begin", "dgrep_job_file_feed", "dgrep_job_file_end",
+    "dgrep_job_finish", "dgrep_job_close", "dgrep_job_stats_get", "dgrep_grep_job_windowed",
 )
 # csrc/kernels/encode_window.h: a long escaped value is cut into chunks of this
 # many bytes, one workgroup each; the default of set_long_value
@@ -140,6 +142,13 @@ class _ReduceBatchOut(ctypes.Structure):
     _fields_ = [("nparts", ctypes.c_uint32), ("total", ctypes.c_uint64),
                 ("part_off", ctypes.POINTER(ctypes.c_uint64)), ("lines_in", ctypes.POINTER(ctypes.c_uint64)),
                 ("bytes", ctypes.c_void_p)]
+
+
+class _JobStats(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in (
+        "files", "packs", "files_packed", "files_windowed", "windows", "rows", "segments", "arena_bytes",
+        "arena_device_bytes", "window_device_bytes", "long_values", "arena_growths")] + [
+        (f, ctypes.c_float) for f in ("scan_ms", "encode_ms", "append_ms", "reduce_ms")]
 
 
 class _BlobInfo(ctypes.Structure):
@@ -301,6 +310,25 @@ def lib() -> ctypes.CDLL:
             L.dgrep_stream_partition_stats.restype = i
             L.dgrep_set_long_value.argtypes = [vp, ctypes.c_uint32]
             L.dgrep_set_long_value.restype = i
+            L.dgrep_job_open.argtypes = [vp, sz, ctypes.c_uint32, ctypes.POINTER(vp)]
+            L.dgrep_job_open.restype = i
+            L.dgrep_job_add.argtypes = [vp, vp, sz, ctypes.c_char_p, sz]
+            L.dgrep_job_add.restype = i
+            L.dgrep_job_file_begin.argtypes = [vp, ctypes.c_char_p, sz]
+            L.dgrep_job_file_begin.restype = i
+            L.dgrep_job_file_feed.argtypes = [vp, vp, sz]
+            L.dgrep_job_file_feed.restype = i
+            L.dgrep_job_file_end.argtypes = [vp]
+            L.dgrep_job_file_end.restype = i
+            L.dgrep_job_finish.argtypes = [vp, ctypes.POINTER(_ReduceBatchOut)]
+            L.dgrep_job_finish.restype = i
+            L.dgrep_job_close.argtypes = [vp]
+            L.dgrep_job_close.restype = None
+            L.dgrep_job_stats_get.argtypes = [vp, ctypes.POINTER(_JobStats), sz]
+            L.dgrep_job_stats_get.restype = i
+            L.dgrep_grep_job_windowed.argtypes = [vp, vp, vp, vp, vp, sz, ctypes.c_uint32, sz,
+                                                  ctypes.POINTER(_ReduceBatchOut)]
+            L.dgrep_grep_job_windowed.restype = i
             _lib = L
     return _lib
 
@@ -717,6 +745,32 @@ class Context:
         self._check(self._L.dgrep_grep_job(self._h, ptrs, lens, fptrs, flens, k, nreduce, ctypes.byref(res)))
         return self._reduce_batch_parts(res)
 
+    def job(self, window: int, nreduce: int) -> "Job":
+        """A windowed whole job (dgrep_job_*): add files of any size in task
+        order, finish() returns every mr-out-<r>."""
+        return Job(self, window, nreduce)
+
+    def grep_job_windowed(self, files, nreduce: int, window: int) -> List[bytes]:
+        """grep_job with no input resident as a whole (dgrep_grep_job_windowed):
+        the same result byte for byte, last_lines_in included, whatever the
+        window. No file: [] without a C call."""
+        files = list(files)
+        if not files:
+            return []
+        as_bytes = lambda x: x.encode("utf-8", "surrogateescape") if isinstance(x, str) else bytes(x)
+        names = [as_bytes(f) for f, _ in files]
+        raws = [as_bytes(c) for _, c in files]
+        k = len(files)
+        bufs = [np.frombuffer(r, dtype=np.uint8) for r in raws]  # keep the bytes alive over the call
+        ptrs = (ctypes.c_void_p * k)(*[b.ctypes.data if len(b) else None for b in bufs])
+        lens = (ctypes.c_size_t * k)(*[len(r) for r in raws])
+        fptrs = (ctypes.c_char_p * k)(*names)
+        flens = (ctypes.c_size_t * k)(*[len(f) for f in names])
+        res = _ReduceBatchOut()
+        self._check(self._L.dgrep_grep_job_windowed(self._h, ptrs, lens, fptrs, flens, k, nreduce, window,
+                                                    ctypes.byref(res)))
+        return self._reduce_batch_parts(res)
+
     def last_reduce_ms(self) -> float:
         """Device time of the last batch reduce (dgrep_last_reduce_ms)."""
         ms = ctypes.c_float()
@@ -884,6 +938,74 @@ class PartitionStream(Stream):
         d.update(rows=int(r.value), out_bytes=int(b.value), long_values=int(lv.value),
                  enc_device_bytes=int(e.value), encode_ms=float(ms.value))
         return d
+
+
+class Job:
+    """dgrep_job_*: the whole grep job over files of any size. add(filename,
+    contents) takes a file held whole; begin(filename), feed(piece)..., end()
+    one that is read piece by piece. finish() returns the content of every
+    mr-out-<r>, byte for byte Context.grep_job of the same files in the same
+    order, and leaves the lines read per partition in ctx.last_lines_in."""
+
+    def __init__(self, ctx: "Context", window: int, nreduce: int):
+        self._L = lib()
+        self.ctx = ctx
+        self.nreduce = nreduce
+        h = ctypes.c_void_p()
+        self._h = h
+        ctx._check(self._L.dgrep_job_open(ctx._h, window, nreduce, ctypes.byref(h)))
+
+    @staticmethod
+    def _bytes(x) -> bytes:
+        return x.encode("utf-8", "surrogateescape") if isinstance(x, str) else bytes(x)
+
+    def add(self, filename, contents):
+        name, raw = self._bytes(filename), self._bytes(contents)
+        buf = np.frombuffer(raw, dtype=np.uint8) if len(raw) else np.zeros(1, np.uint8)
+        self.ctx._check(self._L.dgrep_job_add(self._h, ctypes.c_void_p(buf.ctypes.data), len(raw), name, len(name)))
+
+    def begin(self, filename):
+        name = self._bytes(filename)
+        self.ctx._check(self._L.dgrep_job_file_begin(self._h, name, len(name)))
+
+    def feed(self, piece):
+        raw = self._bytes(piece)
+        buf = np.frombuffer(raw, dtype=np.uint8) if len(raw) else np.zeros(1, np.uint8)
+        self.ctx._check(self._L.dgrep_job_file_feed(self._h, ctypes.c_void_p(buf.ctypes.data), len(raw)))
+
+    def end(self):
+        self.ctx._check(self._L.dgrep_job_file_end(self._h))
+
+    def finish(self) -> List[bytes]:
+        res = _ReduceBatchOut()
+        self.ctx._check(self._L.dgrep_job_finish(self._h, ctypes.byref(res)))
+        return self.ctx._reduce_batch_parts(res)
+
+    def stats(self) -> dict:
+        """dgrep_job_stats_get: files, packs, files by route, windows, rows,
+        segments, arena bytes used and allocated, the window buffers' bytes,
+        long values, arena growths, device ms of scan / encode / append /
+        reduce."""
+        st = _JobStats()
+        self.ctx._check(self._L.dgrep_job_stats_get(self._h, ctypes.byref(st), ctypes.sizeof(st)))
+        return {f: getattr(st, f) for f, _ in _JobStats._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value and self.ctx._h.value:
+            self._L.dgrep_job_close(self._h)
+        self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def build_info() -> str:
@@ -1113,6 +1235,27 @@ def GrepJob(files: Sequence[Tuple[str, object]], nreduce: int) -> List[bytes]:
     if not files:
         return []
     return _context().grep_job(files, nreduce)
+
+
+def GrepJobWindowed(files: Sequence[Tuple[str, object]], nreduce: int, window: int = 64 << 20) -> List[bytes]:
+    """GrepJob for files of any size, with the set pattern (dgrep_job_*): a
+    file's contents may be bytes / str, or an iterable of pieces that is fed as
+    it comes and never held as a whole. Element r is the content of mr-out-<r>;
+    the lines read per partition are left in the context's last_lines_in. No
+    file: [] without touching the GPU."""
+    files = list(files)
+    if not files:
+        return []
+    with _context().job(window, nreduce) as job:
+        for filename, contents in files:
+            if isinstance(contents, (bytes, bytearray, memoryview, str)):
+                job.add(filename, contents)
+                continue
+            job.begin(filename)
+            for piece in contents:
+                job.feed(piece)
+            job.end()
+        return job.finish()
 
 
 def Reduce(key: str, values: Sequence[str]) -> str:

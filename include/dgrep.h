@@ -608,6 +608,104 @@ int dgrep_reduce_batch_device(dgrep_ctx* ctx, const void* d_data, size_t n,
 int dgrep_grep_job(dgrep_ctx* ctx, const uint8_t* const* data, const size_t* n, const char* const* filename,
                    const size_t* fn, size_t nsplits, uint32_t nreduce, dgrep_reduce_batch_out* out);
 
+/* ---- the whole job in windows: files of any size to every mr-out-<r> ----------
+ * dgrep_grep_job needs every input byte resident at once. A job object takes
+ * the same files in the same (task) order without that: a 2 TiB log goes
+ * through windows, 65,536 small files do not each pay for a window of their
+ * own. Two routes, chosen per file:
+ *  - pack: a file given whole (dgrep_job_add) of at most window_bytes joins the
+ *    current pack, the packed buffer of dgrep_scan_batch; a pack's files plus
+ *    one separator between them stay at or below window_bytes. The pack is
+ *    flushed -- one packed ingest, one batch scan, one batch encode of its k
+ *    files with their k filenames -- when the next file does not fit, when a
+ *    file of the other route arrives, and at finish. The job keeps a copy of a
+ *    packed file's bytes: `data` is borrowed for the call only. A long escaped
+ *    line inside a packed file is escaped by one lane, as in
+ *    dgrep_map_partitions_batch.
+ *  - window: a file given whole with n > window_bytes, and every file given by
+ *    begin / feed / end whatever its size, streams through the job's partition
+ *    stream (above: the cut, the carried tail, the parallel long-value path),
+ *    after the pack was flushed.
+ * A flush with a matching line yields k * nreduce cells, a window that completed
+ * a matching line nreduce. They never leave the device: one kernel appends the
+ * bytes to a contiguous arena and the rebased cell boundaries to a device
+ * segment table (segment g belongs to partition g % nreduce), and
+ * dgrep_job_finish runs the batch reduce over both; only the outputs come back.
+ *
+ * Contract: the same files in the same order, by any mix of dgrep_job_add and
+ * begin / feed / end, any cut of a file into feeds and any window_bytes, give
+ * byte for byte what dgrep_grep_job(files, nreduce) returns: bytes, part_off,
+ * lines_in and total. The same filename added twice yields duplicate keys and
+ * the earlier file's line wins, as there.
+ *
+ * Device footprint: the stream's two window buffers (bounded as for a partition
+ * stream of this window: the window plus the longest unfinished line); the
+ * pack buffer (the context's split buffer, at most window_bytes plus 63 of
+ * padding); the scan's and the encoders' per-record scratch; one window's or
+ * one pack's encoded bytes; the arena -- the job's intermediate bytes,
+ * proportional to the matching lines and not to the input, grown geometrically
+ * with its contents kept (old and new exist together for one device copy) and
+ * below twice what is used once past its first 4 KiB; the segment table (8
+ * bytes per segment); at finish the reduce's scratch and output. The window
+ * buffers, the encoder scratch and the encoded-bytes buffer are allocated once
+ * per job; a new file resets only the stream's state.
+ *
+ * DGREP_E_INVALID before any GPU call (dgrep_job_finish and the one-shot with
+ * *out zeroed): null pointers; a bad window_bytes (dgrep_stream_open's rule);
+ * nreduce outside 1..65535; n without data; fn without filename; feed or end
+ * without begin; add, begin or finish inside an open file; any call after
+ * finish; a dgrep_load_dfa on the context since the job was opened (with a
+ * message). No DFA loaded: DGREP_E_NO_DFA. DGREP_E_UNSUPPORTED with a message
+ * naming the limit: 2^32 or more segments; 2^32 or more matching lines in the
+ * job, in one pack or in one window. A HIP error, out-of-memory or a limit
+ * mid-job leaves the job unusable: every later call returns the same status;
+ * dgrep_job_close stays safe. A DGREP_DFA_MATCH_NONE pattern, no matching line,
+ * or no file at all: DGREP_OK with total 0 and all-zero part_off and lines_in;
+ * MATCH_NONE copies nothing. DGREP_DFA_PARTIAL patterns work. At finish the '\n'
+ * counted in the arena must equal the records written, as in dgrep_grep_job.
+ * A job belongs to its context (one call at a time per context) and is closed
+ * before it. After dgrep_job_finish, dgrep_last_scan_stats, dgrep_last_kernel_ms
+ * and dgrep_last_encode_ms report sums over the job's packs and windows,
+ * dgrep_last_reduce_ms the reduce. */
+typedef struct dgrep_job dgrep_job;
+int dgrep_job_open(dgrep_ctx* ctx, size_t window_bytes, uint32_t nreduce, dgrep_job** job);
+/* a whole file held by the caller: any size */
+int dgrep_job_add(dgrep_job* job, const uint8_t* data, size_t n, const char* filename, size_t fn);
+/* a file the caller never holds: begin, feed any number of pieces, end */
+int dgrep_job_file_begin(dgrep_job* job, const char* filename, size_t fn);
+int dgrep_job_file_feed(dgrep_job* job, const uint8_t* data, size_t n);
+int dgrep_job_file_end(dgrep_job* job);
+/* every mr-out-<r>; freed with dgrep_reduce_batch_free */
+int dgrep_job_finish(dgrep_job* job, dgrep_reduce_batch_out* out);
+void dgrep_job_close(dgrep_job* job);
+/* one-shot: open, add every file in order, finish, close */
+int dgrep_grep_job_windowed(dgrep_ctx* ctx, const uint8_t* const* data, const size_t* n, const char* const* filename,
+                            const size_t* fn, size_t nsplits, uint32_t nreduce, size_t window_bytes,
+                            dgrep_reduce_batch_out* out);
+/* What the job did so far (any time between open and close). */
+typedef struct {
+  uint64_t files;               /* files added, both routes */
+  uint64_t packs;               /* packs flushed */
+  uint64_t files_packed;        /* files that took the pack route */
+  uint64_t files_windowed;      /* files that took the window route */
+  uint64_t windows;             /* windows scanned (a file's finish included) */
+  uint64_t rows;                /* rows of nreduce cells in the arena: a flushed file or a window with a match */
+  uint64_t segments;            /* rows * nreduce */
+  uint64_t arena_bytes;         /* intermediate bytes in the arena */
+  uint64_t arena_device_bytes;  /* the arena's capacity now */
+  uint64_t window_device_bytes; /* the two window buffers now (dgrep_stream_stats' data_bytes) */
+  uint64_t long_values;         /* values the window route's parallel long-value path took */
+  uint64_t arena_growths;       /* reallocations of the arena after the first */
+  float scan_ms;                /* device ms, HIP events: scans (dgrep_last_kernel_ms summed) */
+  float encode_ms;              /* the batch and window encoders */
+  float append_ms;              /* the arena appends (the last one counts once a later call waited for it) */
+  float reduce_ms;              /* the batch reduce of dgrep_job_finish */
+} dgrep_job_stats;
+/* Sized getter, as dgrep_last_scan_stats: writes min(out_size, its own size)
+ * bytes and zeroes a larger caller struct's tail; out_size 0 is
+ * DGREP_E_INVALID. Fields are only ever appended. */
+int dgrep_job_stats_get(dgrep_job* job, dgrep_job_stats* out, size_t out_size);
+
 /* Device time (ms, HIP events on the context stream) of the last batch reduce. */
 int dgrep_last_reduce_ms(dgrep_ctx* ctx, float* ms);
 
