@@ -6,6 +6,12 @@
 // bytes; all strings of 3 and 4 bytes over the edge alphabet; 2,000 seeded
 // random strings up to 64 bytes. Every input sits in a heap block of its exact
 // size, so a read outside [0, L) is an ASan report.
+//
+// `escape_width_test --stream` checks nothing itself: it reads values from
+// stdin, each a little-endian u32 length and that many bytes, and writes for
+// each one a u32 length and json_body<true>'s bytes, then a u32 length and the
+// bytes of escape_width_at + escape_put. tests/test_writer_edge_cases.py
+// compares both with the oracle. The values sit in exact-size heap blocks too.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -51,7 +57,48 @@ static bool check(const uint8_t* src, size_t L) {
   return ok;
 }
 
-int main() {
+static bool read_exact(void* p, size_t n) { return n == 0 || fread(p, 1, n, stdin) == n; }
+
+static void write_block(const std::vector<uint8_t>& v, size_t n) {
+  const uint32_t len = uint32_t(n);
+  fwrite(&len, 4, 1, stdout);
+  if (n) fwrite(v.data(), 1, n, stdout);
+}
+
+static int stream() {
+  uint32_t len;
+  long count = 0;
+  while (fread(&len, 4, 1, stdin) == 1) {
+    const size_t L = len;
+    uint8_t* s = static_cast<uint8_t*>(malloc(L ? L : 1));
+    if (!read_exact(s, L)) {
+      fprintf(stderr, "value %ld is cut off\n", count);
+      free(s);
+      return 2;
+    }
+    const uint64_t n = json_body<false>(s, L, nullptr);
+    std::vector<uint8_t> seq(n + 1), local(6 * L + 1, 0xEE);
+    json_body<true>(s, L, seq.data());
+    write_block(seq, n);
+    uint64_t o = 0;
+    for (size_t i = 0; i < L; ++i) {
+      uint8_t w[7];
+      const uint32_t width = dgrep::escape_width_at(s, L, i, w);
+      const uint32_t after = uint32_t(L - 1 - i < 3 ? L - 1 - i : 3);
+      dgrep::escape_put(w, after, width, local.data() + o);  // width <= 6: inside 6 * L
+      o += width;
+    }
+    write_block(local, o);
+    free(s);
+    ++count;
+  }
+  fflush(stdout);
+  fprintf(stderr, "streamed %ld values\n", count);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && strcmp(argv[1], "--stream") == 0) return stream();
   bool ok = true;
   uint8_t b[64];
   for (int a = 0; a < 256; ++a) {
