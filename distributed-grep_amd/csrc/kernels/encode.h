@@ -23,11 +23,15 @@ uint64_t json_escape_host(const uint8_t* s, uint64_t n, uint8_t* out);  // out =
 uint32_t key_prefix_hash(const uint8_t* filename, uint64_t fn);
 
 // Encodes every record's KeyValue line into `out`, partition-major, line order
-// inside a partition. d_bounds (2 * nreduce + 1 u64, device): [p] = begin and
-// [nreduce + p] = end byte of partition p, [2 * nreduce] = total bytes. Lines
+// inside a partition. d_bounds (2 * nreduce + 3 u64, device): [p] = begin and
+// [nreduce + p] = end byte of partition p, [2 * nreduce] = total bytes, then
+// the number of values the chunked path took (escaped values of at least
+// long_value bytes, encode_long.h) and the number of their chunks. Lines
 // past out_cap are not written. With scratch == nullptr or *scratch_bytes too
 // small, only sets *scratch_bytes to the size needed.
-hipError_t encode_partitions(const EncodeArgs& a, void* scratch, size_t* scratch_bytes, uint8_t* out,
-                             uint64_t out_cap, uint64_t* d_bounds, hipStream_t s);
+// a.data need not be aligned, and no byte outside a.data[0, a.n) is read by the
+// chunked path.
+hipError_t encode_partitions(const EncodeArgs& a, uint32_t long_value, void* scratch, size_t* scratch_bytes,
+                             uint8_t* out, uint64_t out_cap, uint64_t* d_bounds, hipStream_t s);
 
 }  // namespace dgrep

@@ -18,6 +18,9 @@
 //      partition; an exclusive scan of the sorted lengths gives each line's
 //      byte offset; partition boundaries give each partition's byte range;
 //   3. write: one wave per 64 lines emits them at their offsets.
+// A value of at least `long_value` bytes that needs escaping is measured and
+// written by the chunked path of encode_long.h, one workgroup per 16 KiB of it;
+// its line's head and tail come from the line writers here.
 // The kernels are built from the device functions of encode_pipeline.h, which
 // the batch writer shares, as it does the host's sort, gather and scan.
 // Algorithmic bytes: the matched lines' bytes read twice (measure, write) +
@@ -44,7 +47,8 @@ namespace {
 // length ASSUMING a plain value (nothing to escape); encode_values_kernel
 // corrects the length of the rare values that need escaping.
 __global__ __launch_bounds__(kEncThreads) void encode_measure_kernel(EncodeArgs a, uint16_t* part, uint32_t* idx,
-                                                                     uint64_t* enc_len) {
+                                                                     uint64_t* enc_len, uint32_t* nchunks) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) nchunks[a.count] = 0;  // the scan's last entry: the total
   for (uint64_t i = uint64_t(blockIdx.x) * kEncThreads + threadIdx.x; i < a.count;
        i += uint64_t(gridDim.x) * kEncThreads) {
     uint8_t d[20];
@@ -56,14 +60,16 @@ __global__ __launch_bounds__(kEncThreads) void encode_measure_kernel(EncodeArgs 
 }
 
 // One WAVE per record (value_needs_escape); a value with anything to escape
-// gets its exact encoded length from json_body (lane 0).
-__global__ __launch_bounds__(kEncThreads) void encode_values_kernel(EncodeArgs a, uint64_t* enc_len) {
+// gets its exact encoded length from json_body (lane 0) if it is short, its
+// chunk count if it is long (value_measured). lo = the buffer's address & 15.
+__global__ __launch_bounds__(kEncThreads) void encode_values_kernel(EncodeArgs a, uint32_t long_value, uint64_t lo,
+                                                                    uint64_t* enc_len, uint32_t* nchunks) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t waves = uint64_t(gridDim.x) * kEncWaves;
   for (uint64_t i = uint64_t(blockIdx.x) * kEncWaves + (threadIdx.x >> 6); i < a.count; i += waves) {
     const uint64_t st = a.start[i], e = st + a.len[i];
-    if (!value_needs_escape(a.data, a.n, st, e, lane)) continue;  // wave-uniform: plain value
-    if (lane == 0) enc_len[i] += json_body<false>(a.data + st, e - st, nullptr) - (e - st);
+    const bool escaped = value_needs_escape(a.data, a.n, st, e, lane, e - st >= long_value);  // wave-uniform
+    value_measured(a.data, st, e, lo + st, escaped, long_value, lane, enc_len + i, nchunks + i);
   }
 }
 
@@ -85,10 +91,12 @@ __global__ __launch_bounds__(kEncThreads) void bounds_kernel(const uint16_t* par
 // and writes its line number's digits to the wave's LDS row; then the wave
 // walks the 64 lines, each broadcast from its lane, and writes it
 // (write_plain_line, the constant head from LDS). A value that needs escaping
-// is written by its own lane alone (write_line_thread).
+// is written by its own lane alone behind that loop (write_line_thread); a long
+// one's bytes are left to the chunk pass, which finds their place in val_pos[record].
 __global__ __launch_bounds__(kEncThreads) void encode_write_kernel(EncodeArgs a, const uint32_t* idx,
                                                                    const uint64_t* pos, const uint64_t* len_sorted,
-                                                                   uint8_t* out, uint64_t out_cap) {
+                                                                   uint32_t* nchunks, uint64_t* val_pos, uint8_t* out,
+                                                                   uint64_t out_cap) {
   __shared__ uint8_t head[kHeadMax];
   __shared__ uint8_t dig[kEncWaves][64][20];
   const uint32_t F = a.fname_json_len, A = 8u + F + 15u;  // head bytes (host guarantees A <= kHeadMax)
@@ -117,14 +125,13 @@ __global__ __launch_bounds__(kEncThreads) void encode_write_kernel(EncodeArgs a,
       const uint64_t str = __shfl(st, int(r), 64), Lr = __shfl(L, int(r), 64);
       const uint32_t ndr = uint32_t(__shfl(int(nd), int(r), 64));
       if (Pr + Tr > out_cap) continue;
-      if (Tr != plain_line_len(F, ndr, Lr)) {  // escaped value: wave-uniform, rare
-        if (lane == r)
-          write_line_thread(a.fname_json, F, a.line_no[i], a.data, a.start[i], a.len[i], out + P, T);
-        continue;
-      }
+      if (Tr != plain_line_len(F, ndr, Lr)) continue;  // escaped value (wave-uniform, rare): below
       write_plain_line(a.data, a.n, out, Pr, Tr, str, Lr, A, ndr, dig[wv][r], lane,
                        [&](uint64_t o) -> uint32_t { return head[o]; });
     }
+    // the escaped lines, each by its own lane, behind the loop so that this path's registers are not the loop's
+    if (jm < a.count && P + T <= out_cap && T != plain_line_len(F, nd, L))
+      write_line_thread(a.fname_json, F, a.line_no[i], a.data, a.start[i], a.len[i], out, P, T, nchunks, val_pos, i);
     __builtin_amdgcn_wave_barrier();  // the LDS digit row is rewritten next round
   }
 }
@@ -132,52 +139,71 @@ __global__ __launch_bounds__(kEncThreads) void encode_write_kernel(EncodeArgs a,
 // the per-thread writer for file names whose head does not fit kHeadMax
 __global__ __launch_bounds__(kEncThreads) void encode_write_thread_kernel(EncodeArgs a, const uint32_t* idx,
                                                                           const uint64_t* pos,
-                                                                          const uint64_t* len_sorted, uint8_t* out,
-                                                                          uint64_t out_cap) {
+                                                                          const uint64_t* len_sorted,
+                                                                          uint32_t* nchunks, uint64_t* val_pos,
+                                                                          uint8_t* out, uint64_t out_cap) {
   for (uint64_t j = uint64_t(blockIdx.x) * kEncThreads + threadIdx.x; j < a.count;
        j += uint64_t(gridDim.x) * kEncThreads) {
     if (pos[j] + len_sorted[j] > out_cap) continue;
     const uint64_t i = idx[j];
-    write_line_thread(a.fname_json, a.fname_json_len, a.line_no[i], a.data, a.start[i], a.len[i], out + pos[j],
-                      len_sorted[j]);
+    write_line_thread(a.fname_json, a.fname_json_len, a.line_no[i], a.data, a.start[i], a.len[i], out, pos[j],
+                      len_sorted[j], nchunks, val_pos, i);
   }
 }
+
+// where record i's value lies (encode_long.h): start[i], as a position
+struct ResidentLoc {
+  const uint64_t* start;
+  uint64_t lo;
+  __device__ uint64_t operator()(uint64_t i) const { return lo + start[i]; }
+};
 }  // namespace
 
-hipError_t encode_partitions(const EncodeArgs& a, void* scratch, size_t* scratch_bytes, uint8_t* out,
-                             uint64_t out_cap, uint64_t* d_bounds, hipStream_t s) {
-  const uint64_t n = a.count;
+hipError_t encode_partitions(const EncodeArgs& a, uint32_t long_value, void* scratch, size_t* scratch_bytes,
+                             uint8_t* out, uint64_t out_cap, uint64_t* d_bounds, hipStream_t s) {
+  const uint64_t n = a.count, max_chunks = long_max_chunks(a.n, n, long_value);
   const int end_bit = key_bits(a.nreduce);
-  size_t tmp = 0;
+  size_t tmp = 0, long_tmp = 0;
   hipError_t e = sort_gather_scan_tmp<uint16_t>(n, end_bit, &tmp, s);
   if (e != hipSuccess) return e;
-  const size_t need = LineTables<uint16_t>::bytes(n) + align256(tmp);
+  if ((e = long_scan_tmp(n, &long_tmp, s)) != hipSuccess) return e;
+  tmp = std::max(tmp, long_tmp);
+  const size_t need = LineTables<uint16_t>::bytes(n) + LongTables::bytes(n, max_chunks) + align256(tmp);
   if (!scratch || *scratch_bytes < need) {
     *scratch_bytes = need;
     return hipSuccess;
   }
   ScratchCarver c{static_cast<uint8_t*>(scratch)};
   const LineTables<uint16_t> q(c, n);
+  const LongTables lq(c, n, max_chunks);
   void* t = c.take<uint8_t>(tmp);
+  uint64_t* val_pos = q.enc_len;  // enc_len is dead once gathered into len_sorted
+  const LongSpan sp = long_span(a.data, a.n);
+  const ResidentLoc loc{a.start, sp.lo};
 
-  e = hipMemsetAsync(d_bounds, 0, (2 * size_t(a.nreduce) + 1) * 8, s);
+  e = hipMemsetAsync(d_bounds, 0, (2 * size_t(a.nreduce) + 3) * 8, s);
   if (e != hipSuccess || n == 0) return e;
   hipLaunchKernelGGL(encode_measure_kernel, dim3(grid_for(n)), dim3(kEncThreads), 0, s, a, q.key_in, q.idx_in,
-                     q.enc_len);
+                     q.enc_len, lq.nchunks);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(encode_values_kernel, dim3(wave_grid_for(n)), dim3(kEncThreads), 0, s, a, q.enc_len);
+  hipLaunchKernelGGL(encode_values_kernel, dim3(wave_grid_for(n)), dim3(kEncThreads), 0, s, a, long_value, sp.lo,
+                     q.enc_len, lq.nchunks);
   if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = long_measure(sp, loc, a.len, n, lq, q.enc_len, d_bounds + 2 * size_t(a.nreduce) + 1, t, tmp, s)) !=
+      hipSuccess)
+    return e;
   if ((e = sort_gather_scan(q, n, end_bit, t, tmp, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(bounds_kernel, dim3(grid_for(n)), dim3(kEncThreads), 0, s, q.key_out, q.pos, q.len_sorted, n,
                      a.nreduce, d_bounds);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (8u + a.fname_json_len + 15u <= kHeadMax)
     hipLaunchKernelGGL(encode_write_kernel, dim3(wave64_grid_for(n)), dim3(kEncThreads), 0, s, a, q.idx_out, q.pos,
-                       q.len_sorted, out, out_cap);
+                       q.len_sorted, lq.nchunks, val_pos, out, out_cap);
   else
     hipLaunchKernelGGL(encode_write_thread_kernel, dim3(grid_for(n)), dim3(kEncThreads), 0, s, a, q.idx_out, q.pos,
-                       q.len_sorted, out, out_cap);
-  return hipGetLastError();
+                       q.len_sorted, lq.nchunks, val_pos, out, out_cap);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return long_write(sp, loc, a.len, n, lq, val_pos, out, s);
 }
 
 }  // namespace dgrep

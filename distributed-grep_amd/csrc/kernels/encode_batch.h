@@ -29,11 +29,14 @@ struct EncodeBatchArgs {
 };
 
 // Encodes every record's KeyValue line into `out`, cell-major, line order
-// inside a cell. d_cell_off (k * nreduce + 1 u64, device) receives the cells'
-// offsets; the last entry is the total. Lines that would end past out_cap are
-// not written. With scratch == nullptr or *scratch_bytes too small, only sets
-// *scratch_bytes to the size needed.
-hipError_t encode_batch(const EncodeBatchArgs& a, void* scratch, size_t* scratch_bytes, uint8_t* out,
-                        uint64_t out_cap, uint64_t* d_cell_off, hipStream_t s);
+// inside a cell. d_cell_off (k * nreduce + 3 u64, device) receives the cells'
+// offsets, entry k * nreduce being the total, then the number of values the
+// chunked path took (escaped values of at least long_value bytes,
+// encode_long.h) and the number of their chunks. Lines that would end past
+// out_cap are not written. With scratch == nullptr or *scratch_bytes too small,
+// only sets *scratch_bytes to the size needed. No byte outside a.data[0, a.n)
+// is read by the chunked path.
+hipError_t encode_batch(const EncodeBatchArgs& a, uint32_t long_value, void* scratch, size_t* scratch_bytes,
+                        uint8_t* out, uint64_t out_cap, uint64_t* d_cell_off, hipStream_t s);
 
 }  // namespace dgrep

@@ -19,7 +19,9 @@
 //      the wave's LDS row; otherwise, or when the head is longer than the row,
 //      head bytes are read from the filename table in global memory (small,
 //      L2-resident). File names of any length are written by the same kernel.
-// A record's value lies at P[begin[split] + start : + len).
+// A record's value lies at P[begin[split] + start : + len). A value of at least
+// `long_value` bytes that needs escaping takes the chunked path of
+// encode_long.h, as in encode.hip.
 #include "encode_batch.h"
 #include "encode_pipeline.h"
 
@@ -27,7 +29,12 @@ namespace dgrep {
 
 namespace {
 __global__ __launch_bounds__(kEncThreads) void batch_measure_kernel(EncodeBatchArgs a, uint32_t* cell, uint32_t* idx,
-                                                                    uint64_t* enc_len) {
+                                                                    uint64_t* enc_len, uint32_t* nchunks,
+                                                                    uint64_t* stats) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    nchunks[a.count] = 0;  // the scan's last entry: the total
+    stats[0] = stats[1] = 0;  // long_fix_kernel counts the long values and their chunks here
+  }
   for (uint64_t i = uint64_t(blockIdx.x) * kEncThreads + threadIdx.x; i < a.count;
        i += uint64_t(gridDim.x) * kEncThreads) {
     const uint32_t sp = a.split[i];
@@ -41,14 +48,16 @@ __global__ __launch_bounds__(kEncThreads) void batch_measure_kernel(EncodeBatchA
 
 // One WAVE per record (value_needs_escape over the value's bytes in P); a value
 // with anything to escape gets its exact encoded length from json_body (lane
-// 0).
-__global__ __launch_bounds__(kEncThreads) void batch_values_kernel(EncodeBatchArgs a, uint64_t* enc_len) {
+// 0) if it is short, its chunk count if it is long (value_measured). lo = P's
+// address & 15.
+__global__ __launch_bounds__(kEncThreads) void batch_values_kernel(EncodeBatchArgs a, uint32_t long_value, uint64_t lo,
+                                                                   uint64_t* enc_len, uint32_t* nchunks) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t waves = uint64_t(gridDim.x) * kEncWaves;
   for (uint64_t i = uint64_t(blockIdx.x) * kEncWaves + (threadIdx.x >> 6); i < a.count; i += waves) {
     const uint64_t st = a.begin[a.split[i]] + a.start[i], e = st + a.len[i];
-    if (!value_needs_escape(a.data, a.n, st, e, lane)) continue;  // wave-uniform: plain value
-    if (lane == 0) enc_len[i] += json_body<false>(a.data + st, e - st, nullptr) - (e - st);
+    const bool escaped = value_needs_escape(a.data, a.n, st, e, lane, e - st >= long_value);  // wave-uniform
+    value_measured(a.data, st, e, lo + st, escaped, long_value, lane, enc_len + i, nchunks + i);
   }
 }
 
@@ -79,10 +88,12 @@ __global__ __launch_bounds__(kEncThreads) void batch_cell_off_kernel(const uint3
 // The head differs per line here: it comes from the wave's LDS row when all the
 // wave's lines share a split and the head fits the row (`staged`,
 // wave-uniform), else from the filename table. A line that would end past
-// out_cap is skipped.
+// out_cap is skipped. A long escaped value's bytes are left to the chunk pass,
+// which finds their place in val_pos[record].
 __global__ __launch_bounds__(kEncThreads) void batch_write_kernel(EncodeBatchArgs a, const uint32_t* idx,
                                                                   const uint64_t* pos, const uint64_t* len_sorted,
-                                                                  uint8_t* out, uint64_t out_cap) {
+                                                                  uint32_t* nchunks, uint64_t* val_pos, uint8_t* out,
+                                                                  uint64_t out_cap) {
   __shared__ uint8_t head[kEncWaves][kHeadMax];
   __shared__ uint8_t dig[kEncWaves][64][20];
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -119,50 +130,69 @@ __global__ __launch_bounds__(kEncThreads) void batch_write_kernel(EncodeBatchArg
       const uint64_t nor = __shfl(no, int(r), 64);
       const uint32_t ndr = uint32_t(__shfl(int(nd), int(r), 64)), Fr = uint32_t(__shfl(int(F), int(r), 64));
       if (Pr + Tr > out_cap) continue;
-      if (Tr != plain_line_len(Fr, ndr, Lr)) {  // escaped value: wave-uniform, rare
-        if (lane == r) write_line_thread(a.names + no, F, a.line_no[i], a.data, src, L, out + P, T);
-        continue;
-      }
+      if (Tr != plain_line_len(Fr, ndr, Lr)) continue;  // escaped value (wave-uniform, rare): below
       write_plain_line(a.data, a.n, out, Pr, Tr, srcr, Lr, 8u + Fr + 15u, ndr, dig[wv][r], lane,
                        [&](uint64_t o) -> uint32_t {
                          if (staged) return head[wv][o];
                          return head_byte(a.names + nor, Fr, o);
                        });
     }
+    // the escaped lines, each by its own lane, behind the loop so that this path's registers are not the loop's
+    if (jm < a.count && P + T <= out_cap && T != plain_line_len(F, nd, L))
+      write_line_thread(a.names + no, F, a.line_no[i], a.data, src, L, out, P, T, nchunks, val_pos, i);
     __builtin_amdgcn_wave_barrier();  // the LDS rows are rewritten next round
   }
 }
+
+// where record i's value lies (encode_long.h): begin[split[i]] + start[i], as a position
+struct BatchLoc {
+  const uint64_t* begin;
+  const uint32_t* split;
+  const uint64_t* start;
+  uint64_t lo;
+  __device__ uint64_t operator()(uint64_t i) const { return lo + begin[split[i]] + start[i]; }
+};
 }  // namespace
 
-hipError_t encode_batch(const EncodeBatchArgs& a, void* scratch, size_t* scratch_bytes, uint8_t* out,
-                        uint64_t out_cap, uint64_t* d_cell_off, hipStream_t s) {
-  const uint64_t n = a.count, cells = a.k * uint64_t(a.nreduce);
+hipError_t encode_batch(const EncodeBatchArgs& a, uint32_t long_value, void* scratch, size_t* scratch_bytes,
+                        uint8_t* out, uint64_t out_cap, uint64_t* d_cell_off, hipStream_t s) {
+  const uint64_t n = a.count, cells = a.k * uint64_t(a.nreduce), max_chunks = long_max_chunks(a.n, n, long_value);
   const int end_bit = key_bits(cells);
-  size_t tmp = 0;
+  size_t tmp = 0, long_tmp = 0;
   hipError_t e = sort_gather_scan_tmp<uint32_t>(n, end_bit, &tmp, s);
   if (e != hipSuccess) return e;
-  const size_t need = LineTables<uint32_t>::bytes(n) + align256(tmp);
+  if ((e = long_scan_tmp(n, &long_tmp, s)) != hipSuccess) return e;
+  tmp = std::max(tmp, long_tmp);
+  const size_t need = LineTables<uint32_t>::bytes(n) + LongTables::bytes(n, max_chunks) + align256(tmp);
   if (!scratch || *scratch_bytes < need) {
     *scratch_bytes = need;
     return hipSuccess;
   }
   ScratchCarver c{static_cast<uint8_t*>(scratch)};
   const LineTables<uint32_t> q(c, n);
+  const LongTables lq(c, n, max_chunks);
   void* t = c.take<uint8_t>(tmp);
+  uint64_t* val_pos = q.enc_len;  // enc_len is dead once gathered into len_sorted
+  uint64_t* stats = d_cell_off + cells + 1;
+  const LongSpan sp = long_span(a.data, a.n);
+  const BatchLoc loc{a.begin, a.split, a.start, sp.lo};
 
-  if (n == 0) return hipMemsetAsync(d_cell_off, 0, (cells + 1) * 8, s);
+  if (n == 0) return hipMemsetAsync(d_cell_off, 0, (cells + 3) * 8, s);
   hipLaunchKernelGGL(batch_measure_kernel, dim3(grid_for(n)), dim3(kEncThreads), 0, s, a, q.key_in, q.idx_in,
-                     q.enc_len);
+                     q.enc_len, lq.nchunks, stats);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(batch_values_kernel, dim3(wave_grid_for(n)), dim3(kEncThreads), 0, s, a, q.enc_len);
+  hipLaunchKernelGGL(batch_values_kernel, dim3(wave_grid_for(n)), dim3(kEncThreads), 0, s, a, long_value, sp.lo,
+                     q.enc_len, lq.nchunks);
   if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = long_measure(sp, loc, a.len, n, lq, q.enc_len, stats, t, tmp, s)) != hipSuccess) return e;
   if ((e = sort_gather_scan(q, n, end_bit, t, tmp, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(batch_cell_off_kernel, dim3(grid_for(cells + 1)), dim3(kEncThreads), 0, s, q.key_out, q.pos,
                      q.len_sorted, n, cells, d_cell_off);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(batch_write_kernel, dim3(wave64_grid_for(n)), dim3(kEncThreads), 0, s, a, q.idx_out, q.pos,
-                     q.len_sorted, out, out_cap);
-  return hipGetLastError();
+                     q.len_sorted, lq.nchunks, val_pos, out, out_cap);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return long_write(sp, loc, a.len, n, lq, val_pos, out, s);
 }
 
 }  // namespace dgrep

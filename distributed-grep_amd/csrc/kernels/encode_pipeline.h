@@ -3,7 +3,8 @@
 // hash and plain length, the per-thread line writer, the plain line's dword
 // assembly with the head byte fetched through a callable (write_plain_line),
 // gather_len_kernel, the grids, the scratch carver, the per-record tables and
-// the host's "sort by key, gather the lengths, scan them". The window writer
+// the host's "sort by key, gather the lengths, scan them". A long escaped value
+// takes the chunked path of encode_long.h in both. The window writer
 // (encode_window.hip) still carries its own copy (DESIGN 3.13 says why). All
 // of it sits in an unnamed namespace, as in reduce_common.h.
 #pragma once
@@ -13,6 +14,7 @@
 #include <algorithm>
 
 #include "encode_common.h"
+#include "encode_long.h"
 
 namespace dgrep {
 namespace {
@@ -24,9 +26,10 @@ constexpr uint32_t kHeadMax = 2048;  // LDS bytes of a staged line head `{"Key":
 // One WAVE per value: its bytes data[st, e) are tested 4 per lane (aligned
 // dwords, SWAR) and a ballot decides, so consecutive lanes read consecutive
 // dwords and a value is one coalesced sweep. Returns whether anything needs
-// escaping (wave-uniform).
+// escaping (wave-uniform). `early` (wave-uniform): leave at the first escape
+// seen, so that a long escaped value is not swept to its end by this one wave.
 __device__ __forceinline__ bool value_needs_escape(const uint8_t* data, uint64_t n, uint64_t st, uint64_t e,
-                                                   uint32_t lane) {
+                                                   uint32_t lane, bool early) {
   bool bad = false;
   for (uint64_t w = (st & ~uint64_t(3)) + 4u * lane; w < e; w += 256) {
     uint32_t x;
@@ -38,8 +41,26 @@ __device__ __forceinline__ bool value_needs_escape(const uint8_t* data, uint64_t
     }
     const uint32_t in = (w >= st && w + 4 <= e) ? 0x80808080u : range_mask(w, st, e);
     bad = bad || (special_bytes(x) & in) != 0u;
+    // (every lane still in the loop sees the same ballot and leaves with the others)
+    if (early && __ballot(bad) != 0ull) break;
   }
   return __ballot(bad) != 0ull;
+}
+
+// What a values kernel does with record i once its wave knows whether the
+// value data[st, e) needs escaping: a long escaped value (at least long_value
+// bytes; vst = its position, encode_long.h) only gets its chunk count, a short
+// one its exact encoded length from json_body (lane 0).
+__device__ __forceinline__ void value_measured(const uint8_t* data, uint64_t st, uint64_t e, uint64_t vst, bool escaped,
+                                               uint32_t long_value, uint32_t lane, uint64_t* enc_len,
+                                               uint32_t* nchunks) {
+  if (lane != 0) return;
+  if (escaped && e - st >= long_value) {
+    *nchunks = uint32_t(long_chunk_count(vst, vst + (e - st)));
+  } else {
+    *nchunks = 0;
+    if (escaped) *enc_len += json_body<false>(data + st, e - st, nullptr) - (e - st);
+  }
 }
 
 // ihash of the key "<file> (line number #<line_no>)": FNV-1a continued from h0
@@ -71,14 +92,21 @@ __device__ __forceinline__ void wave_publish_lds() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// One thread writes one record's line of enc bytes at o (the values that need
+// One thread writes one record's line of enc bytes at out + P (the values that need
 // escaping, and every line of a file name past the LDS head). st and len are
 // REFERENCES on purpose: a caller that passes a table entry (a.start[i]) has
 // it loaded where the line needs it, after the head's stores, which loads
 // cannot move past; loaded before the call they cost the resident write kernel
-// 27 VGPRs.
+// 27 VGPRs. nchunks[i] = the record's chunk count (encode_long.h): not 0 for a
+// long value, whose bytes are left to the chunk pass; its place in out goes to
+// val_pos[i] and kLongPlaced into the count. The wave writers call it behind
+// their loop over the wave's lines, every escaped line's lane at once: called
+// inside that loop its registers were the loop's (123 VGPRs instead of 96 in
+// the resident write kernel, one wave per SIMD fewer).
 __device__ void write_line_thread(const uint8_t* name, uint32_t F, uint64_t line_no, const uint8_t* data,
-                                  const uint64_t& st, const uint64_t& len, uint8_t* o, uint64_t enc) {
+                                  const uint64_t& st, const uint64_t& len, uint8_t* out, uint64_t P, uint64_t enc,
+                                  uint32_t* nchunks, uint64_t* val_pos, uint64_t i) {
+  uint8_t* o = out + P;
   put_str(o, "{\"Key\":\"");
   for (uint32_t k = 0; k < F; ++k) *o++ = name[k];
   put_str(o, " (line number #");
@@ -87,7 +115,11 @@ __device__ void write_line_thread(const uint8_t* name, uint32_t F, uint64_t line
   for (uint32_t k = 0; k < nd; ++k) *o++ = uint8_t('0' + d[k]);
   put_str(o, ")\",\"Value\":\"");
   const uint64_t L = len;
-  if (enc == plain_line_len(F, nd, L)) {
+  if (nchunks[i] != 0u) {
+    val_pos[i] = uint64_t(o - out);
+    nchunks[i] |= kLongPlaced;
+    o += enc - plain_line_len(F, nd, 0);
+  } else if (enc == plain_line_len(F, nd, L)) {
     copy_bytes(o, data + st, L);
     o += L;
   } else {

@@ -21,6 +21,11 @@ static_assert(kLongChunk % kLongStep == 0 && kLongChunk >= kLongStep, "whole wor
 // from 256 bytes on, the smallest length the setter admits, for one value alone
 // and for a window full of them; so the default is that floor.
 constexpr uint32_t kLongValueDefault = 256;
+// The same default for the resident and the batch writer (encode_long.h), whose
+// one-lane path runs every escaped line's lane at once: measured (DESIGN §3.13,
+// round 17), a split full of escaped values is faster by one lane each below 768
+// bytes a value and by chunks from there on.
+constexpr uint32_t kLongValueResidentDefault = 768;
 
 struct WindowEncodeArgs {
   EncodeArgs e;         // data = the window buffer, records in the WINDOW's coordinates

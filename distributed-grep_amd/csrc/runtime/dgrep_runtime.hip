@@ -218,7 +218,8 @@ struct dgrep_ctx {
   uint8_t* d_enc_out = nullptr;
   uint64_t enc_out_cap = 0;
   float last_encode_ms = 0.f;
-  uint32_t long_value = 0;  // dgrep_set_long_value: 0 = kLongValueDefault (the window encoder only)
+  uint32_t long_value = 0;  // dgrep_set_long_value: 0 = each writer's default (kLongValueDefault, kLongValueResidentDefault)
+  dgrep_encode_stats enc_stats = {};  // dgrep_last_encode_stats (encode_ms is filled in by the getter)
 
   // many splits in one scan (dgrep_scan_batch*, kernels/batch.h)
   uint64_t* d_bat_begin = nullptr;  // [k + 1]
@@ -2899,7 +2900,7 @@ static int encode_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, cons
   json_escape_host(fname, fn, fjson.data());
   if ((rc = grow(c, &c->d_fname, &c->fname_cap, fj + 1)) != DGREP_OK) return rc;
   HIPCHK(hipMemcpyAsync(c->d_fname, fjson.data(), fj + 1, hipMemcpyHostToDevice, c->stream));
-  if ((rc = grow(c, &c->d_bounds, &c->bounds_cap, 2 * uint64_t(nreduce) + 1)) != DGREP_OK) return rc;
+  if ((rc = grow(c, &c->d_bounds, &c->bounds_cap, 2 * uint64_t(nreduce) + 3)) != DGREP_OK) return rc;
   EncodeArgs a;
   a.data = d_data;
   a.n = n;
@@ -2911,14 +2912,15 @@ static int encode_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, cons
   a.fname_json_len = uint32_t(fj);
   a.key_hash0 = key_prefix_hash(fname, fn);
   a.nreduce = nreduce;
+  const uint32_t long_value = c->long_value ? c->long_value : kLongValueResidentDefault;
   size_t need = 0;
-  HIPCHK(encode_partitions(a, nullptr, &need, nullptr, 0, nullptr, c->stream));
+  HIPCHK(encode_partitions(a, long_value, nullptr, &need, nullptr, 0, nullptr, c->stream));
   if ((rc = grow(c, &c->d_enc_scratch, &c->enc_scratch_cap, need)) != DGREP_OK) return rc;
   size_t have = c->enc_scratch_cap;
   HIPCHK(hipEventRecord(c->ev0, c->stream));
-  HIPCHK(encode_partitions(a, c->d_enc_scratch, &have, d_out, out_cap, c->d_bounds, c->stream));
+  HIPCHK(encode_partitions(a, long_value, c->d_enc_scratch, &have, d_out, out_cap, c->d_bounds, c->stream));
   HIPCHK(hipEventRecord(c->ev1, c->stream));
-  std::vector<uint64_t> b(2 * size_t(nreduce) + 1);
+  std::vector<uint64_t> b(2 * size_t(nreduce) + 3);  // the long values and their chunks ride back with the bounds
   HIPCHK(hipMemcpyAsync(b.data(), c->d_bounds, b.size() * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipEventElapsedTime(&c->last_encode_ms, c->ev0, c->ev1));
@@ -2927,6 +2929,9 @@ static int encode_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, cons
     end[p] = b[nreduce + p];
   }
   *total = b[2 * size_t(nreduce)];
+  c->enc_stats.records = count;
+  c->enc_stats.long_values = b[2 * size_t(nreduce) + 1];
+  c->enc_stats.long_chunks = b[2 * size_t(nreduce) + 2];
   return DGREP_OK;
 }
 
@@ -3032,6 +3037,7 @@ static int encode_batch_resident(dgrep_ctx* c, const uint8_t* d_packed, uint64_t
                                  uint64_t out_cap, uint64_t* cell_off, uint64_t* total) {
   const uint64_t cells = k * uint64_t(nreduce);
   *total = 0;
+  c->enc_stats = dgrep_encode_stats{};
   if (count == 0) {
     if (cell_off) memset(cell_off, 0, (cells + 1) * 8);
     c->last_encode_ms = 0.f;
@@ -3039,7 +3045,7 @@ static int encode_batch_resident(dgrep_ctx* c, const uint8_t* d_packed, uint64_t
   }
   int rc;
   if ((rc = grow(c, &c->d_bat_names, &c->bat_names_cap, names.size())) != DGREP_OK) return rc;
-  if ((rc = grow(c, &c->d_bat_cells, &c->bat_cells_cap, cells + 1)) != DGREP_OK) return rc;
+  if ((rc = grow(c, &c->d_bat_cells, &c->bat_cells_cap, cells + 3)) != DGREP_OK) return rc;
   HIPCHK(hipMemcpyAsync(c->d_bat_begin, c->bat_begin.data(), (k + 1) * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->d_bat_names, names.data(), names.size(), hipMemcpyHostToDevice, c->stream));
   EncodeBatchArgs a;
@@ -3056,18 +3062,24 @@ static int encode_batch_resident(dgrep_ctx* c, const uint8_t* d_packed, uint64_t
   a.name_hash = reinterpret_cast<const uint32_t*>(c->d_bat_names + (k + 1) * 8);
   a.names = c->d_bat_names + (k + 1) * 8 + k * 4;
   a.nreduce = nreduce;
+  const uint32_t long_value = c->long_value ? c->long_value : kLongValueResidentDefault;
   size_t need = 0;
-  HIPCHK(encode_batch(a, nullptr, &need, nullptr, 0, nullptr, c->stream));
+  HIPCHK(encode_batch(a, long_value, nullptr, &need, nullptr, 0, nullptr, c->stream));
   if ((rc = grow(c, &c->d_enc_scratch, &c->enc_scratch_cap, need)) != DGREP_OK) return rc;
   size_t have = c->enc_scratch_cap;
   HIPCHK(hipEventRecord(c->ev0, c->stream));
-  HIPCHK(encode_batch(a, c->d_enc_scratch, &have, d_out, out_cap, c->d_bat_cells, c->stream));
+  HIPCHK(encode_batch(a, long_value, c->d_enc_scratch, &have, d_out, out_cap, c->d_bat_cells, c->stream));
   HIPCHK(hipEventRecord(c->ev1, c->stream));
+  uint64_t long_stats[2] = {0, 0};  // the long values and their chunks ride back with the offsets
+  HIPCHK(hipMemcpyAsync(long_stats, c->d_bat_cells + cells + 1, 16, hipMemcpyDeviceToHost, c->stream));
   if (cell_off) HIPCHK(hipMemcpyAsync(cell_off, c->d_bat_cells, (cells + 1) * 8, hipMemcpyDeviceToHost, c->stream));
   else HIPCHK(hipMemcpyAsync(total, c->d_bat_cells + cells, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipEventElapsedTime(&c->last_encode_ms, c->ev0, c->ev1));
   if (cell_off) *total = cell_off[cells];
+  c->enc_stats.records = count;
+  c->enc_stats.long_values = long_stats[0];
+  c->enc_stats.long_chunks = long_stats[1];
   return DGREP_OK;
 }
 
@@ -3503,6 +3515,7 @@ struct dgrep_job {
   int status = DGREP_OK;  // a failure mid-job: every later call returns it
   bool finished = false, in_file = false;
   dgrep_stream* s = nullptr;  // the window route: buffers, scratch and d_enc live as long as the job
+  dgrep_encode_stats enc_sum = {};  // over the packs' encodes: dgrep_last_encode_stats after dgrep_job_finish
   // the open pack (host): P = f_0 '\n' f_1 ... as job_plan.h lays it out, and its files
   uint8_t* pack = nullptr;
   size_t pack_cap = 0;
@@ -3638,6 +3651,9 @@ static int job_flush(dgrep_job* j) {
     if ((rc = grow(c, &c->d_enc_out, &c->enc_out_cap, (enc_total + enc_total / 16 + 15) & ~uint64_t(15))) != DGREP_OK)
       return rc;
   }
+  j->enc_sum.records += c->enc_stats.records;  // the pack's last attempt
+  j->enc_sum.long_values += c->enc_stats.long_values;
+  j->enc_sum.long_chunks += c->enc_stats.long_chunks;
   return job_append_rows(j, c->d_enc_out, enc_total, c->d_bat_cells + 1, k * uint64_t(j->plan.nreduce), false, k, count);
 }
 
@@ -3892,6 +3908,7 @@ extern "C" int dgrep_job_finish(dgrep_job* j, dgrep_reduce_batch_out* out) {
     return rc;
   }
   j->finished = true;
+  c->enc_stats = j->enc_sum;  // the sums over the job's packs
   return DGREP_OK;
 }
 
@@ -3949,6 +3966,21 @@ extern "C" int dgrep_last_reduce_ms(dgrep_ctx* c, float* ms) {
 extern "C" int dgrep_last_encode_ms(dgrep_ctx* c, float* ms) {
   if (!c || !ms) return DGREP_E_INVALID;
   *ms = c->last_encode_ms;
+  return DGREP_OK;
+}
+
+extern "C" int dgrep_last_encode_stats(dgrep_ctx* c, dgrep_encode_stats* out, size_t out_size) {
+  if (!c || !out || out_size == 0) return DGREP_E_INVALID;
+  dgrep_encode_stats st;
+  memset(&st, 0, sizeof st);  // the padding behind encode_ms too
+  st.records = c->enc_stats.records;
+  st.long_values = c->enc_stats.long_values;
+  st.long_chunks = c->enc_stats.long_chunks;
+  st.encode_ms = c->last_encode_ms;
+  // a shorter (older) caller layout gets its own size; a longer one a zeroed tail
+  const size_t k = std::min(out_size, sizeof st);
+  memcpy(out, &st, k);
+  if (out_size > k) memset(reinterpret_cast<uint8_t*>(out) + k, 0, out_size - k);
   return DGREP_OK;
 }
 

@@ -68,11 +68,13 @@ EXPORTS = (
     "dgrep_map_partitions_windowed", "dgrep_stream_partition_stats", "dgrep_set_long_value",
     "dgrep_job_open", "dgrep_job_add", "dgrep_job_file_begin", "dgrep_job_file_feed", "dgrep_job_file_end",
     "dgrep_job_finish", "dgrep_job_close", "dgrep_job_stats_get", "dgrep_grep_job_windowed",
+    "dgrep_last_encode_stats",
 )
 # csrc/kernels/encode_window.h: a long escaped value is cut into chunks of this
 # many bytes, one workgroup each; the default of set_long_value
 LONG_CHUNK = 16384
 LONG_VALUE_DEFAULT = 256
+LONG_VALUE_RESIDENT_DEFAULT = 768  # kLongValueResidentDefault: the resident and the batch writer
 STREAM_VALUES = 1
 STREAM_BOUNDED = 2
 COMM_ID_BYTES = 128
@@ -151,6 +153,11 @@ class _JobStats(ctypes.Structure):
         (f, ctypes.c_float) for f in ("scan_ms", "encode_ms", "append_ms", "reduce_ms")]
 
 
+class _EncodeStats(ctypes.Structure):
+    _fields_ = [("records", ctypes.c_uint64), ("long_values", ctypes.c_uint64), ("long_chunks", ctypes.c_uint64),
+                ("encode_ms", ctypes.c_float)]
+
+
 class _BlobInfo(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_uint32), ("nstates", ctypes.c_uint32), ("nclasses", ctypes.c_uint32),
                 ("start", ctypes.c_uint32), ("start_m", ctypes.c_uint32)]
@@ -224,6 +231,8 @@ def lib() -> ctypes.CDLL:
             L.dgrep_encode_device.restype = i
             L.dgrep_last_encode_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
             L.dgrep_last_encode_ms.restype = i
+            L.dgrep_last_encode_stats.argtypes = [vp, ctypes.POINTER(_EncodeStats), sz]
+            L.dgrep_last_encode_stats.restype = i
             L.dgrep_reduce.argtypes = [vp, vp, sz, ctypes.POINTER(_ReduceOut)]
             L.dgrep_reduce.restype = i
             L.dgrep_reduce_free.argtypes = [ctypes.POINTER(_ReduceOut)]
@@ -588,8 +597,10 @@ class Context:
 
     def set_long_value(self, n: int = 0):
         """Testing/tuning: the value length from which an escaped value takes the
-        window encoder's parallel path (dgrep_set_long_value; 0 = the default,
-        else a multiple of 64 in [256, 2^30]). Only the windowed writer reads it."""
+        partition writers' parallel path (dgrep_set_long_value; 0 = each writer's
+        default, 256 for the window writer and 768 for the resident and batch ones,
+        else a multiple of 64 in [256, 2^30]). All three writers (resident,
+        batch, window) read it; 2^30 forces the one-lane path everywhere."""
         self._check(self._L.dgrep_set_long_value(self._h, n))
 
     def map_partitions_windowed(self, filename, contents, nreduce: int, window: int) -> List[bytes]:
@@ -781,6 +792,14 @@ class Context:
         ms = ctypes.c_float()
         self._check(self._L.dgrep_last_encode_ms(self._h, ctypes.byref(ms)))
         return float(ms.value)
+
+    def encode_stats(self) -> dict:
+        """dgrep_last_encode_stats: records, long_values and long_chunks of the
+        last resident or batch encode (after a job: the sums over its packs),
+        and its device ms. A window-route encode does not touch it."""
+        st = _EncodeStats()
+        self._check(self._L.dgrep_last_encode_stats(self._h, ctypes.byref(st), ctypes.sizeof(st)))
+        return {f: getattr(st, f) for f, _ in _EncodeStats._fields_}
 
     def last_kernel_ms(self) -> float:
         ms = ctypes.c_float()

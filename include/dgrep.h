@@ -168,19 +168,41 @@ typedef struct {
 } dgrep_partitions;
 
 /* Host split -> ingest -> scan -> encode -> host partitions (the Map +
- * writeMapOutput of one map task). */
+ * writeMapOutput of one map task). A value that needs escaping and has at
+ * least `long value` bytes (dgrep_set_long_value) is escaped by many workgroups
+ * at once; dgrep_last_encode_stats says how many values took that path. */
 int dgrep_map_partitions(dgrep_ctx* ctx, const uint8_t* data, size_t n, const char* filename, size_t fn,
                          uint32_t nreduce, dgrep_partitions* out);
 void dgrep_partitions_free(dgrep_partitions* p);
 /* Device form over dgrep_scan_device's records: writes into d_out (out_cap
  * bytes; *total receives the bytes needed -- if larger, call again with a
- * bigger buffer); part_begin/part_end are host arrays of nreduce entries. */
+ * bigger buffer); part_begin/part_end are host arrays of nreduce entries.
+ * d_data need not be aligned; the long-value path reads no byte outside
+ * d_data[0, n) and writes no byte of a line that does not fit below out_cap.
+ * Its tables are sized for values that lie apart, as a scan's do: where records
+ * made by hand overlap so that their chunks outnumber them, the values that do
+ * not fit are escaped by one lane each (same bytes, at 2.6 MB/s a value). */
 int dgrep_encode_device(dgrep_ctx* ctx, const void* d_data, size_t n, const uint64_t* d_line_no,
                         const uint64_t* d_start, const uint64_t* d_len, uint64_t count, const char* filename,
                         size_t fn, uint32_t nreduce, void* d_out, uint64_t out_cap, uint64_t* part_begin,
                         uint64_t* part_end, uint64_t* total);
 /* Device time (ms) of the last encode (HIP events on the context stream). */
 int dgrep_last_encode_ms(dgrep_ctx* ctx, float* ms);
+/* What the last encode of dgrep_map_partitions, dgrep_encode_device,
+ * dgrep_map_partitions_batch, dgrep_encode_batch_device or dgrep_grep_job did.
+ * Where a call retries with a larger buffer, the last attempt, not the sum.
+ * After dgrep_job_finish: the sums over the job's packs. An encode of the
+ * window route (partition streams, a job's windows) does not touch it. */
+typedef struct {
+  uint64_t records;      /* records of the last resident or batch encode */
+  uint64_t long_values;  /* values the chunked (many-workgroup) path took */
+  uint64_t long_chunks;  /* their chunks */
+  float encode_ms;       /* = dgrep_last_encode_ms */
+} dgrep_encode_stats;
+/* Sized getter, as dgrep_last_scan_stats: writes min(out_size, its own size)
+ * bytes, a larger caller struct gets its tail zeroed, out_size 0 is
+ * DGREP_E_INVALID; fields are only ever appended. */
+int dgrep_last_encode_stats(dgrep_ctx* ctx, dgrep_encode_stats* out, size_t out_size);
 
 /* ---- reduce task (map_reduce/worker.go:22-68,161-165; grep.go:38-40) ------
  * One reduce task of the grep job on the GPU: `data` = the concatenated
@@ -469,9 +491,9 @@ void dgrep_batch_partitions_free(dgrep_batch_partitions* p);
  * is the sum over the call's windows.
  *
  * A value that needs escaping and has at least `long value` bytes
- * (dgrep_set_long_value) is escaped by many workgroups at once, not by one
- * lane as in dgrep_map_partitions: minified JSON, binaries and logs with
- * embedded blobs are what windows are for.
+ * (dgrep_set_long_value) is escaped by many workgroups at once, as in
+ * dgrep_map_partitions: minified JSON, binaries and logs with embedded blobs
+ * cost what their bytes cost.
  *
  * DGREP_E_INVALID before any GPU call, result zeroed: the checks of
  * dgrep_stream_open / dgrep_stream_feed; filename == NULL with fn != 0; nreduce
@@ -497,10 +519,12 @@ int dgrep_map_partitions_windowed(dgrep_ctx* ctx, const uint8_t* data, size_t n,
 int dgrep_stream_partition_stats(dgrep_stream* stream, uint64_t* rows, uint64_t* out_bytes, uint64_t* long_values,
                                  uint64_t* enc_device_bytes, float* encode_ms);
 /* Tests / tuning, like dgrep_set_lane_chunk: the value length at and above
- * which an escaped value takes the window encoder's parallel path. 0 = the
- * built-in default; else a multiple of 64 in [256, 2^30]; anything else is
- * DGREP_E_INVALID and leaves the setting unchanged. Affects only the window
- * encoder. */
+ * which an escaped value takes the partition writers' parallel path. 0 = the
+ * built-in default (256 in the window writer, 768 in the resident and the
+ * batch writer); else a multiple of 64 in [256, 2^30]; anything else is
+ * DGREP_E_INVALID and leaves the setting unchanged. Governs all three writers
+ * (resident, batch, window) and what is built on them; 2^30 forces the
+ * one-lane path everywhere. */
 int dgrep_set_long_value(dgrep_ctx* ctx, uint32_t bytes);
 
 /* Device form: the records exactly as dgrep_scan_batch_device returned them
@@ -517,7 +541,9 @@ int dgrep_set_long_value(dgrep_ctx* ctx, uint32_t bytes);
  * d_packed, split lengths that do not add up to n_packed), `count` without the
  * four record arrays, out_cap without d_out, and the filename and nreduce
  * checks above. DGREP_E_UNSUPPORTED: nsplits * nreduce >= 2^32 or count >=
- * 2^32. dgrep_last_encode_ms reports the encode's device time. */
+ * 2^32. dgrep_last_encode_ms reports the encode's device time. Long escaped
+ * values take the parallel path as in dgrep_encode_device: no byte outside
+ * d_packed[0, n_packed) is read. */
 int dgrep_encode_batch_device(dgrep_ctx* ctx, const void* d_packed, size_t n_packed,
                               const uint64_t* split_len /* host, nsplits */, size_t nsplits,
                               const uint64_t* d_line_no, const uint64_t* d_start, const uint64_t* d_len,
@@ -620,7 +646,7 @@ int dgrep_grep_job(dgrep_ctx* ctx, const uint8_t* const* data, const size_t* n, 
  *    files with their k filenames -- when the next file does not fit, when a
  *    file of the other route arrives, and at finish. The job keeps a copy of a
  *    packed file's bytes: `data` is borrowed for the call only. A long escaped
- *    line inside a packed file is escaped by one lane, as in
+ *    line inside a packed file takes the parallel long-value path, as in
  *    dgrep_map_partitions_batch.
  *  - window: a file given whole with n > window_bytes, and every file given by
  *    begin / feed / end whatever its size, streams through the job's partition
@@ -666,7 +692,8 @@ int dgrep_grep_job(dgrep_ctx* ctx, const uint8_t* const* data, const size_t* n, 
  * A job belongs to its context (one call at a time per context) and is closed
  * before it. After dgrep_job_finish, dgrep_last_scan_stats, dgrep_last_kernel_ms
  * and dgrep_last_encode_ms report sums over the job's packs and windows,
- * dgrep_last_reduce_ms the reduce. */
+ * dgrep_last_encode_stats the sums over its packs, dgrep_last_reduce_ms the
+ * reduce. */
 typedef struct dgrep_job dgrep_job;
 int dgrep_job_open(dgrep_ctx* ctx, size_t window_bytes, uint32_t nreduce, dgrep_job** job);
 /* a whole file held by the caller: any size */
