@@ -2,6 +2,17 @@
 #pragma once
 #include <stdint.h>
 
+#include "pattern_layout.h"
+
+// This header also compiles as plain C++ (the host-only pattern image builder
+// and its stand-alone driver): no HIP qualifiers there, and uint2 only named
+#ifdef __HIPCC__
+#define DGREP_HD __host__ __device__
+#else
+#define DGREP_HD
+struct uint2;
+#endif
+
 namespace dgrep {
 
 // One matching line as produced by a tile, before global ordering.
@@ -23,13 +34,13 @@ constexpr uint32_t kRelBits = 23;
 constexpr uint32_t kMetaCand = 1u << 23;
 constexpr uint32_t kMetaPend = 1u << 24;
 constexpr uint32_t kLenHiShift = 25;
-__host__ __device__ inline uint32_t meta_of(uint32_t rel, uint64_t len, bool cand) {
+DGREP_HD inline uint32_t meta_of(uint32_t rel, uint64_t len, bool cand) {
   return rel | (cand ? kMetaCand : 0u) | (uint32_t(len >> 32) << kLenHiShift);
 }
-__host__ __device__ inline uint64_t staged_len(const StagedLine& L) {
+DGREP_HD inline uint64_t staged_len(const StagedLine& L) {
   return uint64_t(L.len_lo) | (uint64_t(L.meta >> kLenHiShift) << 32);
 }
-__host__ __device__ inline uint32_t staged_rel(const StagedLine& L) { return L.meta & ((1u << kRelBits) - 1u); }
+DGREP_HD inline uint32_t staged_rel(const StagedLine& L) { return L.meta & ((1u << kRelBits) - 1u); }
 
 // Per-tile bookkeeping written by the scan kernel.
 struct TileInfo {
@@ -153,8 +164,7 @@ struct LongArgs {
 
 // the filter stepper's parked lines on the whole DFA (long_dfa_* kernels):
 // each segment is run from up to kLongGuesses distinct entry guesses, the
-// states its lookback leads to from kLongSeeds start states
-constexpr int kLongSeeds = 8;
+// states its lookback leads to from kLongSeeds (pattern_layout.h) start states
 constexpr int kLongGuesses = 4;
 constexpr uint32_t kNoGuess = 0xffffffffu;
 struct LongDfaArgs {
@@ -178,7 +188,7 @@ struct LongDfaArgs {
   uint64_t npend;
   // the whole-DFA LDS image of a u16 DFA (runtime build_ximg; nullptr: the
   // first rows in LDS, the rest read from `full`): x_hot rows (plus extra
-  // rows), then a DfaXRec per state >= x_hot at byte xr_off
+  // rows), then a DfaXRec (pattern_layout.h) per state >= x_hot at byte xr_off
   const uint8_t* ximg;
   uint32_t ximg_bytes, x_hot, xr_off;
   // [2] long_dfa_fix_kernel's tallies (dgrep_scan_stats long_segments,
@@ -186,13 +196,6 @@ struct LongDfaArgs {
   // of them no guess fitted (re-run from the true state); one add per line
   unsigned long long* walk_count;
 };
-// DfaXRec: a state past the LDS image's first rows reads the row of a resident
-// DEFAULT state except in at most two classes (keyword automata: 4,608 of
-// config 4's 4,978 such states differ in one class, 367 in two; the 2 left
-// get an extra row of their own as default): x = default row | class 1 << 16
-// | class 2 << 24 (0xff: unused), y = next state on class 1 | on class 2 << 16.
-constexpr uint32_t kXNone = 0xffu;
-
 // verify_kernel's arguments (kStepFilter): the whole DFA with the blob's ids
 struct VerifyArgs {
   const uint8_t* data;
@@ -236,30 +239,6 @@ constexpr uint32_t kSlotLong = 0x7fffffffu;
 
 constexpr int kScanThreads = 256;  // 4 waves per workgroup
 constexpr int kTileLanes = 64;     // a tile is one wave's 64 chunks
-
-// DFA stepper selected by dgrep_load_dfa from the state count.
-enum : int {
-  kStepTable = 0,   // <= 256 states: u8 [state][byte] table, 260-byte rows
-  kStepSheng8 = 1,  // <= 8 states: per-byte 8-state vectors (v_perm stepping)
-  // 2: the r01 wide stepper (u16 rows, cold ones from HBM on the chain), removed in round 6
-  kStepPair = 3,    // 2 * states * classes^2 <= kPairMaxT2 bytes: two input bytes per table lookup
-  kStepFilter = 4,  // > 256 states: the DFA's shallow part in LDS, lines that leave it verified afterwards
-  // 5: the r05 word stepper (one lookup per 4-byte word), measured slower than pair; removed in round 6
-};
-
-// LDS image of kStepFilter: byte classes [256] (u8), then u16 [state][class]
-// rows of the filter DFA (its states premultiplied by the class count), at
-// most this many bytes in all -- with 1024 threads x 4 slots x 8 B the
-// workgroup stays within the CU's 160 KiB.
-#ifndef DGREP_FILTER_KIB
-#define DGREP_FILTER_KIB 124
-#endif
-constexpr uint32_t kFilterImageBytes = DGREP_FILTER_KIB * 1024;
-// u8 classes: four byte values share a dword, so printable ASCII (0x20-0x7f)
-// spans 24 dwords in 24 distinct banks and a wave's class reads of text never
-// conflict (tools/lds_bank_bench.hip on the log corpus: u8 table 0 % conflict
-// cycles, u32 entries at 4*b 52 %, u64 at 8*b 55 %). C4 kernel 3.18 -> 3.38 TB/s.
-constexpr uint32_t kFilterClassBytes = 256;
 
 // StepPair's T2 entries are u32 (ds_read_b32) when the whole image fits
 // kPairW32MaxImage, else u16 (DGREP_PAIR_T2_U32=0: always u16). A u16 chain

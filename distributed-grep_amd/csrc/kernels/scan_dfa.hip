@@ -150,7 +150,9 @@ __device__ __forceinline__ uint32_t hi_byte(uint32_t m) { return (31u - __clz(m)
 // LDS row stride of the u8 transition table: 256 bytes + 4. Row s starts at
 // s*260, so byte b of state s sits in bank (s + b/4) mod 32: lanes in
 // different states that read the same input byte hit different banks.
+// The image builder lays the rows out at kTableRow (pattern_layout.h).
 constexpr uint32_t kRow = 260;
+static_assert(kRow == kTableRow, "the table stepper's row stride and the image's");
 
 template <int TBL, int E, int NT, bool MAPS = false>
 struct ScanSmem {
@@ -1796,7 +1798,6 @@ struct FullDfa {
   }
 };
 
-constexpr uint32_t kVerifyHotBytes = 48 * 1024;
 constexpr uint32_t kVerifyLookback = 256;  // bytes a wave-verified segment's entry state is guessed from
 
 // The tile loop shared by both verification kernels: line_matches(a, e)
@@ -2460,8 +2461,6 @@ static_assert(kLongSeedsRun >= 1 && kLongSeedsRun <= kLongSeeds, "DGREP_LONG_SEE
 // rows (breadth-first: the states keyword text spends its bytes in; C4's
 // depth <= 3 rows need ~110 KiB) -- the segment lanes' table reads stay in LDS
 constexpr int kLongDfaThreads = 1024;
-constexpr uint32_t kLongDfaHotBytes = 120 * 1024;  // rows alone (u32 DFAs)
-constexpr uint32_t kLongDfaLdsBytes = 158 * 1024;  // rows + DfaXRec (u16 DFAs)
 
 // One segment per lane, read in 64-byte blocks (four 16-B loads, the next
 // block in flight while this one is stepped). Two segments per lane in
@@ -2793,7 +2792,6 @@ __global__ __launch_bounds__(256) void order_lines_kernel(const TileInfo* tiles,
 // ---- host-side launchers (called from dgrep_runtime.cpp) ----------------
 
 #if DG_PART(0)
-uint32_t scan_table_row() { return kRow; }
 uint32_t scan_max_lane_chunk() { return uint32_t(kMaxLaneChunk); }
 #endif
 
@@ -3048,8 +3046,6 @@ hipError_t order_lines(const TileInfo* tiles, const StagedLine* staging, uint64_
   return hipGetLastError();
 }
 
-uint32_t verify_hot_bytes() { return kVerifyHotBytes; }
-
 hipError_t long_lines_end(const LongArgs& la, hipStream_t stream) {
   uint64_t grid = (la.npend + 3) / 4;
   if (grid > 16384) grid = 16384;
@@ -3077,9 +3073,6 @@ hipError_t long_lines_sheng(const LongArgs& la, hipStream_t stream) {
 
 uint32_t long_lookback() { return kLongLookback; }
 uint32_t long_guesses() { return uint32_t(kLongGuesses); }
-uint32_t long_seeds() { return uint32_t(kLongSeeds); }
-uint32_t long_dfa_hot_bytes() { return kLongDfaHotBytes; }
-uint32_t long_dfa_lds_bytes() { return kLongDfaLdsBytes; }
 
 hipError_t long_lines_dfa(const LongDfaArgs& la, bool u32, hipStream_t stream) {
   if (la.nseg) {

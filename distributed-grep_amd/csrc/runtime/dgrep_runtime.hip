@@ -33,16 +33,13 @@
 #include "../kernels/window.h"
 #include "job_plan.h"
 #include "pack_pieces.h"
+#include "pattern_image.h"
 
 // DFAs of at most this many states use the Sheng stepper (8 = its limit; 0
-// sends every DFA of <= 256 states to the table stepper)
+// sends every DFA of <= 256 states to the table stepper). The stand-alone
+// builder takes the same default from pattern_layout.h, included above.
 #ifndef DGREP_SHENG_MAX_STATES
 #define DGREP_SHENG_MAX_STATES 8
-#endif
-// DFAs above the Sheng limit whose two-byte table fits in LDS use the pair
-// stepper (0: they use the u8 table stepper)
-#ifndef DGREP_PAIR_ENABLE
-#define DGREP_PAIR_ENABLE 1
 #endif
 // matching-line records per resident thread of the HBM spill area the
 // one-chunk-per-lane steppers move full LDS slots to (0: no spilling)
@@ -62,12 +59,19 @@
 #ifndef DGREP_SHENG_MAPS
 #define DGREP_SHENG_MAPS 1
 #endif
+// A/B knobs: long_dfa_seg1_kernel and verify_kernel (one 1024-thread workgroup
+// per CU) read the whole-DFA LDS image (build_ximg) when the pattern has one
+#ifndef DGREP_LONG_XREC
+#define DGREP_LONG_XREC 1
+#endif
+#ifndef DGREP_VERIFY_XREC
+#define DGREP_VERIFY_XREC 1
+#endif
 namespace dgrep {
 // scan_dfa.hip
 uint64_t scan_tile_bytes(int kind, uint32_t table_bytes, uint64_t n, uint64_t resident_blocks, uint32_t force,
                          double density, uint32_t spill_per_lane, uint32_t* chunk, uint32_t* waves_per_block,
                          uint32_t* slots, uint32_t* threads, bool* spills);
-uint32_t scan_table_row();
 uint32_t scan_max_lane_chunk();
 hipError_t scan_dfa_occupancy(int kind, uint32_t table_bytes, int* blocks_per_cu);
 hipError_t scan_dfa(int kind, const ScanArgs& a, int grid, hipStream_t stream);
@@ -81,11 +85,7 @@ hipError_t long_lines_resolve(const LongArgs& la, hipStream_t stream);
 hipError_t long_lines_sheng(const LongArgs& la, hipStream_t stream);
 hipError_t long_lines_dfa(const LongDfaArgs& la, bool u32, hipStream_t stream);
 uint32_t long_lookback();
-uint32_t long_dfa_hot_bytes();
-uint32_t long_dfa_lds_bytes();
 uint32_t long_guesses();
-uint32_t long_seeds();
-uint32_t verify_hot_bytes();
 }  // namespace dgrep
 
 using namespace dgrep;
@@ -93,10 +93,27 @@ using namespace dgrep;
 constexpr size_t kCounters = 8;
 constexpr size_t kCtrLongWalk = 5;  // [5], [6]: long_dfa_fix_kernel's segments walked / re-run
 
-// StepPair image offsets and thresholds (see StepPair in scan_dfa.hip)
-struct PairArgs {
-  uint32_t t1 = 0, thr = 0, div = 0, w32 = 0;
+// The loaded pattern's device buffers: each the upload of the PatternImage
+// vector of its name (null where that is empty).
+struct PatternDevice {
+  uint8_t* table = nullptr;  // the stepper's image
+  void* full = nullptr;
+  uint8_t* cls = nullptr;    // [256] byte classes, with `full`
+  uint8_t* ximg = nullptr;
+  uint32_t* nfa = nullptr;
+  uint8_t* long_tbl = nullptr;
+  uint32_t* st2id = nullptr;
+  // carry_ensure's uploads: the plain DFA; cls [256], then absorbing [nstates]
+  void* carry_trans = nullptr;
+  uint8_t* carry_aux = nullptr;
 };
+
+static void free_pattern_device(PatternDevice* d) {
+  void* bufs[] = {d->table, d->full, d->cls, d->ximg, d->nfa, d->long_tbl, d->st2id, d->carry_trans, d->carry_aux};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+  *d = PatternDevice();
+}
 
 struct dgrep_ctx {
   int device = 0;
@@ -105,36 +122,18 @@ struct dgrep_ctx {
   hipStream_t stream = nullptr;
   std::string err;
 
-  // loaded pattern
+  // loaded pattern (dgrep_load_dfa): its host side -- the vectors that were
+  // uploaded dropped, h_trans and long_seed kept -- and its device buffers
   bool loaded = false;
-  uint64_t load_gen = 0;  // dgrep_load_dfa calls: a stream opened under another pattern is refused (dgrep_stream_*)
-  uint32_t flags = 0, nstates = 0, start = 0, start_m = 0;
-  bool empty_line_matches = false;
-  uint8_t* d_table = nullptr;  // stepper image (see dgrep_load_dfa)
-  uint32_t table_bytes = 0;
-  uint32_t nclasses = 0;
+  uint64_t load_gen = 0;  // successful loads: a stream opened under another pattern is refused (dgrep_stream_*)
+  PatternImage pat;
+  PatternDevice dev;
+  int blocks_per_cu = 1;
   // dgrep_set_stepper: force a stepper (0 auto, 2 u8 table, 3 pair, 4 filter) /
   // cap the filter stepper's LDS rows (tests, tuning)
   int force_stepper = 0;
   uint32_t filter_rows_cap = UINT32_MAX;
   uint32_t lane_chunk = 0;  // dgrep_set_lane_chunk (0 = adaptive)
-  int step_kind = kStepTable;
-  PairArgs pair_args;
-  // kStepFilter: CAND_END (premultiplied), and the whole DFA for verify_kernel
-  uint32_t cand_end = UINT32_MAX;
-  void* d_full = nullptr;      // [nstates][nclasses], the blob's ids: u16, or u32 above 65535 states
-  bool full_u32 = false;
-  uint8_t* d_cls = nullptr;    // [256]
-  uint32_t blob_start = 0, blob_start_m = 0;  // start / start_m in d_full's (breadth-first) ids
-  uint32_t blob_matched = UINT32_MAX;          // the absorbing accepting state in d_full's ids (none: UINT32_MAX)
-  uint32_t blob_dead = UINT32_MAX;             // the absorbing rejecting state (none: UINT32_MAX)
-  std::vector<uint32_t> long_seed;             // lookback start states of long_dfa_seg1_kernel (d_full's ids)
-  uint32_t verify_hot = 0;                     // leading entries of d_full verify_kernel keeps in LDS
-  uint8_t* d_ximg = nullptr;                   // the whole-DFA LDS image (build_ximg; u16 DFAs that fit)
-  uint32_t ximg_bytes = 0, x_hot = 0, x_rec = 0, xr_off = 0;
-  uint32_t* d_nfa = nullptr;                   // DGREP_DFA_PARTIAL: the NFA program (verify_nfa_kernel)
-  uint32_t nfa_words = 0;                      // its position-set words
-  int blocks_per_cu = 1;
 
   // per-scan scratch (grown on demand, reused)
   TileInfo* d_tiles = nullptr;
@@ -156,14 +155,9 @@ struct dgrep_ctx {
   uint64_t chunk_nl_cap = 0;
   ChunkMap* d_chunk_map = nullptr;  // Sheng: per-chunk maps (ScanArgs::chunk_map)
   uint64_t chunk_map_cap = 0;
-  uint32_t sheng_nl_lo = 0, sheng_nl_hi = 0;  // Sheng: V['\n']
   PendingLine* d_pend = nullptr;   // parked long lines
   uint64_t pend_cap = 0;
-  // long lines: the blob's u8 [S][256] table and stepper state -> blob state
-  // (only for <= 256-state DFAs on the Sheng / pair / table steppers)
-  uint8_t* d_long_tbl = nullptr;
-  uint32_t* d_st2id = nullptr;
-  uint32_t long_start_m = 0, long_states = 0;
+  // long lines (dev.long_tbl / dev.st2id on the Sheng, pair and table steppers)
   LongSeg* d_seg = nullptr;
   uint64_t seg_cap = 0;
   uint64_t* d_seg_off = nullptr;
@@ -258,23 +252,12 @@ struct dgrep_ctx {
   uint8_t* h_job_pack = nullptr;
   size_t h_job_pack_cap = 0;
 
-  // The blob's plain DFA, kept on the host for a bounded stream's carry walk
-  // (kernels/carry.h): uploaded the first time a stream folds, so a context
-  // that never folds pays only these host bytes.
-  std::vector<uint32_t> h_trans;
-  uint8_t h_cls[256] = {};
-  uint32_t h_nstates = 0, h_nclasses = 0, h_start = 0, h_start_m = 0;
-  void* d_carry_trans = nullptr;
-  uint8_t* d_carry_aux = nullptr;  // cls [256], then absorbing [nstates]
+  // a bounded stream's carry walk (kernels/carry.h) over pat.h_trans: uploaded
+  // to dev.carry_* the first time a stream folds, so a context that never
+  // folds pays only the host bytes
   CarryTable carry;
   bool carry_ready = false;
 };
-
-// the kind handed to the scan entry points: the stepper, with kKindW32 for the
-// pair stepper's u32-entry image
-static int launch_kind(const dgrep_ctx* c) {
-  return c->step_kind | (c->step_kind == kStepPair && c->pair_args.w32 ? kKindW32 : 0);
-}
 
 namespace {
 
@@ -308,225 +291,6 @@ int grow(dgrep_ctx* c, T** p, uint64_t* cap, uint64_t need) {
 #ifndef DGREP_SYNC_SPIN_US
 #define DGREP_SYNC_SPIN_US 1000
 #endif
-
-// The LDS image through which long_dfa_seg1_kernel and verify_kernel read a
-// whole u16 DFA F ([S][K], breadth-first ids) with no HBM access on the chain:
-// rows [0, H) whole; then one DfaXRec (scan_common.h) for each state in
-// [H, S) -- its default = the resident row differing from its own in the
-// fewest classes (exhaustive, stopping at one difference; config 4: 30 ms),
-// with the <= 2 differing classes as exceptions; a state no resident row
-// comes within two classes of gets its own row after the first H (an EXTRA
-// row, its record's default, no exceptions). Layout: rows (H + X) * K u16,
-// records at *xr_off (8-aligned). H is the most rows that leave room for
-// everything within `budget`; false if even 64 rows do not (the kernels then
-// keep the first rows and read the rest from HBM).
-#ifndef DGREP_LONG_XREC
-#define DGREP_LONG_XREC 1
-#endif
-// verify_kernel on the same LDS image (one 1024-thread workgroup per CU)
-#ifndef DGREP_VERIFY_XREC
-#define DGREP_VERIFY_XREC 1
-#endif
-static bool build_ximg(const uint16_t* F, uint32_t S, uint32_t K, uint32_t budget, std::vector<uint8_t>* img,
-                       uint32_t* hot, uint32_t* xr_off) {
-  const uint64_t row = 2ull * K;
-  if (K >= kXNone || row <= 8 || budget < 8ull * S + 64 * row + 8) return false;
-  uint64_t H = std::min<uint64_t>(S, (budget - 8 - 8ull * S) / (row - 8));
-  for (int attempt = 0; attempt < 8 && H >= 64; ++attempt) {
-    const uint64_t R = S - H;
-    std::vector<uint2> rec(R);
-    std::vector<uint32_t> extra;
-    for (uint64_t j = 0; j < R; ++j) {
-      const uint16_t* f = F + (H + j) * K;
-      uint32_t best = 3, bd = 0;
-      for (uint64_t d = 0; d < H && best > 1; ++d) {
-        const uint16_t* g = F + d * K;
-        uint32_t diff = 0;
-        for (uint32_t k = 0; k < K && diff < best; ++k) diff += f[k] != g[k];
-        if (diff < best) { best = diff; bd = uint32_t(d); }
-      }
-      if (best > 2) {
-        rec[j] = make_uint2(uint32_t(H + extra.size()) | (kXNone << 16) | (kXNone << 24), 0u);
-        extra.push_back(uint32_t(H + j));
-        continue;
-      }
-      uint32_t cl[2] = {kXNone, kXNone}, nx[2] = {0, 0}, e = 0;
-      const uint16_t* g = F + uint64_t(bd) * K;
-      for (uint32_t k = 0; k < K; ++k)
-        if (f[k] != g[k]) { cl[e] = k; nx[e] = f[k]; ++e; }
-      rec[j] = make_uint2(bd | (cl[0] << 16) | (cl[1] << 24), nx[0] | (nx[1] << 16));
-    }
-    const uint64_t off = ((H + extra.size()) * row + 7) & ~7ull, bytes = (off + 8 * R + 15) & ~15ull;
-    if (bytes > budget || H + extra.size() > 0xffffu) {
-      H -= std::min<uint64_t>(H, (bytes - budget) / (row - 8) + 1 + extra.size());
-      continue;
-    }
-    img->assign(bytes, 0);
-    memcpy(img->data(), F, H * row);
-    for (size_t x = 0; x < extra.size(); ++x) memcpy(img->data() + (H + x) * row, F + uint64_t(extra[x]) * K, row);
-    memcpy(img->data() + off, rec.data(), 8 * R);
-    *hot = uint32_t(H);
-    *xr_off = uint32_t(off);
-    return true;
-  }
-  return false;
-}
-
-// The pair stepper's LDS image (StepPair, scan_dfa.hip) from the blob's DFA:
-// C u8 [256] (byte -> esz class), T2 u32 (u16 if the image exceeds 16 KiB) [S'][K][K] at kPairT2 (two
-// bytes per lookup), T1 u16 [S'][K] (single bytes); states premultiplied to
-// their T2 row's LDS address (kPairT2 + id * 2K^2). S' = S + shadows: a pair whose FIRST byte is a '\n'
-// entering start_m hides that event in the state between its bytes, so it
-// leads to shadow(y) -- a copy of y = T[start_m][c2] -- instead of y. Ids:
-// the states other than start_m, then the shadows of y != start_m, then
-// start_m, then shadow(start_m): a pair-end id >= first shadow holds an
-// event. Returns false if the DFA does not fit (T2 > kPairMaxT2 bytes).
-bool build_pair_image(const dgrep_blob_header& h, const uint32_t* trans, std::vector<uint8_t>* img, uint32_t* start,
-                      uint32_t* start_m, PairArgs* pa, std::vector<uint32_t>* orig_out) {
-  const uint32_t S = h.nstates, K = h.nclasses, M = h.start_m;
-  const uint32_t cn = h.byte_class[uint8_t('\n')];
-  auto T = [&](uint32_t s, uint32_t c) { return trans[size_t(s) * K + c]; };
-  // shadow targets, in class order
-  std::vector<uint32_t> shadow_of(S, UINT32_MAX);  // original state -> shadow id
-  std::vector<uint32_t> targets;
-  bool any_flag = false;
-  for (uint32_t s = 0; s < S; ++s) any_flag = any_flag || T(s, cn) == M;
-  if (any_flag)
-    for (uint32_t c = 0; c < K; ++c) {
-      const uint32_t y = T(M, c);
-      if (std::find(targets.begin(), targets.end(), y) == targets.end()) targets.push_back(y);
-    }
-  const uint32_t Sp = S + uint32_t(targets.size());
-  // T2 entry: u32 when the image fits kPairW32MaxImage, else u16. Bytes per T2
-  // row: esz K^2, padded to an ODD number of dwords so that the same column of
-  // different rows falls in different LDS banks
-  auto row_of = [&](uint64_t esz) { return ((esz * K * K + 3) & ~3ull) | 4ull; };
-  auto end_of = [&](uint64_t r) {
-    const uint64_t t1 = (kPairT2 + r * Sp + 15) & ~15ull;
-    return std::make_pair(t1, (t1 + 2ull * Sp * K + 15) & ~15ull);
-  };
-  uint32_t esz = DGREP_PAIR_T2_U32 && end_of(row_of(4)).second <= kPairW32MaxImage ? 4u : 2u;
-  const uint64_t row = row_of(esz);
-  if (row * Sp > kPairMaxT2) return false;
-  const uint64_t t1_off = end_of(row).first, end = end_of(row).second;
-  if (end > kPairMaxImage) return false;
-  std::vector<uint32_t> id(S), orig(Sp);
-  uint32_t next = 0;
-  for (uint32_t s = 0; s < S; ++s)
-    if (s != M) { id[s] = next; orig[next++] = s; }
-  const bool m_shadow = std::find(targets.begin(), targets.end(), M) != targets.end();
-  for (uint32_t y : targets)
-    if (y != M) { shadow_of[y] = next; orig[next++] = y; }
-  id[M] = next;
-  orig[next++] = M;
-  if (m_shadow) { shadow_of[M] = next; orig[next++] = M; }
-  // ids S-1 .. S'-1: the shadows of y != start_m, start_m, shadow(start_m)
-  const uint32_t thr_id = S - 1;
-  auto premul = [&](uint32_t i) { return uint16_t(kPairT2 + uint64_t(i) * row); };
-  img->assign(end, 0);
-  uint8_t* const t2 = img->data() + kPairT2;
-  uint16_t* t1 = reinterpret_cast<uint16_t*>(img->data() + t1_off);
-  for (uint32_t i = 0; i < Sp; ++i) {
-    const uint32_t x = orig[i];
-    for (uint32_t c1 = 0; c1 < K; ++c1) {
-      const uint32_t a = T(x, c1);
-      const bool flagged = c1 == cn && a == M;
-      t1[size_t(i) * K + c1] = premul(id[a]);
-      for (uint32_t c2 = 0; c2 < K; ++c2) {
-        const uint32_t y = T(a, c2);
-        const uint16_t v = premul(flagged ? shadow_of[y] : id[y]);
-        uint8_t* const e = t2 + size_t(i) * row + esz * (size_t(c1) * K + c2);
-        if (esz == 4) {
-          const uint32_t v32 = v;
-          memcpy(e, &v32, 4);
-        } else {
-          memcpy(e, &v, 2);
-        }
-      }
-    }
-  }
-  // one u8 table C[b] = esz class(b) at LDS 0; esz (K - 1) < 256; and (for
-  // the pair's first byte) CK[b] = esz K class(b), u16 at kPairCK
-  if (esz * (K - 1u) > 255u) return false;
-  for (int b = 0; b < 256; ++b) {
-    img->data()[b] = uint8_t(esz * h.byte_class[b]);
-    const uint16_t ck = uint16_t(esz * K * h.byte_class[b]);
-    memcpy(img->data() + kPairCK + 2 * b, &ck, 2);
-  }
-  *start = premul(id[h.start]);
-  *start_m = premul(id[M]);
-  *orig_out = orig;  // pair state index -> blob state (a shadow -> the state it copies)
-  pa->t1 = uint32_t(t1_off);
-  pa->thr = premul(thr_id);
-  pa->div = uint32_t(row);
-  pa->w32 = esz == 4 ? 1u : 0u;
-  return true;
-}
-
-#ifndef DGREP_FILTER_PITCH
-#define DGREP_FILTER_PITCH 1
-#endif
-// The filter stepper's LDS image (StepFilter, scan_dfa.hip): byte classes (kFilterClassBytes),
-// then u16 rows of the DFA's first
-// R - 2 states in breadth-first order from start (start_m at depth 0), as many
-// rows as kFilterImageBytes holds, plus CAND (every transition out of them;
-// '\n' -> CAND_END) and CAND_END (start's row). Ids: kept states other than
-// start_m, CAND, start_m, CAND_END; entries premultiplied by K. Returns false
-// if not even start, start_m and their successors fit.
-// `excluded`: a partial blob's CAND state (never kept, so every transition
-// into it is a filter CAND too).
-bool build_filter_image(const dgrep_blob_header& h, const uint32_t* trans, uint32_t row_cap, std::vector<uint8_t>* img,
-                        uint32_t* start, uint32_t* start_m, uint32_t* cand_end, uint32_t excluded = UINT32_MAX) {
-  const uint32_t S = h.nstates, K = h.nclasses, M = h.start_m;
-  const uint32_t cn = h.byte_class[uint8_t('\n')];
-  // row pitch P >= K entries with P / 2 odd (DGREP_FILTER_PITCH): consecutive
-  // rows start an odd number of dwords apart, so the rows a wave's lanes sit in
-  // cover the 32 banks in turn (a CPU model of config 4's chain reads: 5.8 ->
-  // 5.6 LDS cycles per read)
-  const uint32_t P = DGREP_FILTER_PITCH ? ((K + 1) & ~1u) + (((K + 1) & 2u) ? 0u : 2u) : K;
-  // rows that fit (row_cap: dgrep_set_stepper's test knob)
-  const uint32_t R = std::min<uint32_t>((kFilterImageBytes - kFilterClassBytes) / (2 * P), row_cap);
-  if (R < 4 || uint64_t(R) * P > 65535) return false;
-  std::vector<uint32_t> order;
-  std::vector<uint8_t> seen(S, 0);
-  auto visit = [&](uint32_t x) {
-    if (!seen[x] && x != excluded) { seen[x] = 1; order.push_back(x); }
-  };
-  visit(h.start);
-  visit(M);
-  for (size_t q = 0; q < order.size(); ++q)
-    for (uint32_t k = 0; k < K; ++k) visit(trans[size_t(order[q]) * K + k]);
-  const bool part = excluded != UINT32_MAX;
-  const uint32_t keep = std::min<uint32_t>(uint32_t(order.size()), S <= R && !part ? S : R - 2);
-  if (keep < 2) return false;
-  std::vector<uint32_t> id(S, UINT32_MAX);
-  uint32_t next = 0;
-  for (uint32_t i = 0; i < keep; ++i)
-    if (order[i] != M) id[order[i]] = next++;
-  const bool exact = keep == S && !part;  // the whole DFA fits: no candidates
-  const uint32_t CAND = exact ? UINT32_MAX : next++;
-  id[M] = next++;
-  const uint32_t CEND = exact ? UINT32_MAX : next++;
-  const uint32_t Sf = next;
-  auto to = [&](uint32_t x) { return uint16_t((id[x] == UINT32_MAX ? CAND : id[x]) * P); };
-  img->assign((kFilterClassBytes + size_t(Sf) * P * 2 + 15) & ~size_t(15), 0);
-  for (int b = 0; b < 256; ++b) img->data()[b] = h.byte_class[b];
-  uint16_t* rows = reinterpret_cast<uint16_t*>(img->data() + kFilterClassBytes);
-  for (uint32_t i = 0; i < keep; ++i) {
-    const uint32_t x = order[i];
-    for (uint32_t k = 0; k < K; ++k) rows[size_t(id[x]) * P + k] = to(trans[size_t(x) * K + k]);
-  }
-  if (!exact) {
-    for (uint32_t k = 0; k < K; ++k) {
-      rows[size_t(CAND) * P + k] = uint16_t((k == cn ? CEND : CAND) * P);
-      rows[size_t(CEND) * P + k] = to(trans[size_t(h.start) * K + k]);
-    }
-  }
-  *start = id[h.start] * P;
-  *start_m = id[M] * P;
-  *cand_end = exact ? UINT32_MAX : CEND * P;
-  return true;
-}
 
 }  // namespace
 
@@ -585,12 +349,13 @@ extern "C" void dgrep_close(dgrep_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  void* bufs[] = {c->d_table, c->d_full, c->d_ximg, c->d_nfa, c->d_cls, c->d_spill, c->d_tails, c->d_chunk_nl, c->d_chunk_map,
-                  c->d_pend, c->d_long_tbl, c->d_st2id, c->d_seg, c->d_seg_off, c->d_segmap, c->d_seg_from, c->d_seg_state, c->d_tiles, c->d_out_off, c->d_line_base, c->d_staging, c->d_counters,
+  free_pattern_device(&c->dev);
+  void* bufs[] = {c->d_spill, c->d_tails, c->d_chunk_nl, c->d_chunk_map,
+                  c->d_pend, c->d_seg, c->d_seg_off, c->d_segmap, c->d_seg_from, c->d_seg_state, c->d_tiles, c->d_out_off, c->d_line_base, c->d_staging, c->d_counters,
                   c->d_overflow, c->d_data, c->d_res_line, c->d_res_start, c->d_res_len, c->d_enc_scratch,
                   c->d_fname, c->d_bounds, c->d_enc_out, c->d_red_scratch, c->d_red_out, c->d_bat_begin,
                   c->d_bat_lines, c->d_bat_sums, c->d_res_split, c->d_res_sbegin, c->d_bat_names, c->d_bat_cells,
-                  c->d_rb_seg, c->d_rb_off, c->d_carry_trans, c->d_carry_aux};
+                  c->d_rb_seg, c->d_rb_off};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
@@ -655,241 +420,48 @@ extern "C" int dgrep_set_stepper(dgrep_ctx* c, int force, uint32_t filter_rows) 
   return DGREP_OK;
 }
 
+// vector -> a fresh device allocation (a multiple of 16 bytes); an empty vector leaves *p null
+template <class P, class V>
+static hipError_t upload(const std::vector<V>& v, P** p) {
+  if (v.empty()) return hipSuccess;
+  const size_t bytes = v.size() * sizeof(V);
+  const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), (bytes + 15) & ~size_t(15));
+  return e != hipSuccess ? e : hipMemcpy(*p, v.data(), bytes, hipMemcpyHostToDevice);
+}
+
+// build (host only, pattern_image.h) -> upload into fresh allocations -> commit:
+// until the last step the context holds the previous pattern, whole (dgrep.h)
 extern "C" int dgrep_load_dfa(dgrep_ctx* c, const void* blob, size_t n) {
   if (!c) return DGREP_E_INVALID;
-  dgrep_blob_info info;
-  if (dgrep_blob_info_get(blob, n, &info) != DGREP_OK) {
-    c->err = "dgrep_load_dfa: malformed blob";
-    return DGREP_E_INVALID;
+  PatternImage img;
+  std::string err;
+  const int rc = build_pattern_image(blob, n, c->force_stepper, c->filter_rows_cap, &img, &err);
+  if (rc != DGREP_OK) {
+    c->err = err;
+    return rc;
   }
-  HIPCHK(hipSetDevice(c->device));
-  dgrep_blob_header h;
-  memcpy(&h, blob, sizeof h);
-  const uint32_t* trans = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(blob) + sizeof h);
-  for (size_t i = 0; i < size_t(h.nstates) * h.nclasses; ++i)
-    if (trans[i] >= h.nstates) {
-      c->err = "dgrep_load_dfa: transition out of range";
-      return DGREP_E_INVALID;
-    }
-  // expand byte classes into the kernel's LDS image
-  std::vector<uint8_t> t;
-  uint32_t start = h.start, start_m = h.start_m;
-  const int force = c->force_stepper;
-  // a partial DFA (DGREP_DFA_PARTIAL) runs only as a filter: its last state is
-  // CAND, and the NFA program after `trans` verifies the lines that reach it
-  const bool partial = (h.flags & DGREP_DFA_PARTIAL) != 0;
-  if (partial && force != 0 && force != 4) {
-    c->err = "dgrep_load_dfa: a partial DFA (over the compiler's state budget) runs on the filter stepper only";
-    return DGREP_E_UNSUPPORTED;
-  }
-  std::vector<uint8_t> pair_img;
-  uint32_t pair_start = 0, pair_m = 0;
-  std::vector<uint32_t> st2id;  // stepper state index -> blob state (long lines, see resolve_long_lines)
-  const bool want_pair =
-      !partial && ((force == 0 && h.nstates > DGREP_SHENG_MAX_STATES && DGREP_PAIR_ENABLE) || force == 3);
-  const bool pair_ok = want_pair && build_pair_image(h, trans, &pair_img, &pair_start, &pair_m, &c->pair_args, &st2id);
-  if (force == 3 && !pair_ok) {
-    c->err = "dgrep_load_dfa: the pair stepper's two-byte table does not fit this DFA";
-    return DGREP_E_UNSUPPORTED;
-  }
-  std::vector<uint8_t> filter_img;
-  uint32_t f_start = 0, f_m = 0, f_cend = UINT32_MAX;
-  const bool filter_ok = !pair_ok && ((force == 0 && (h.nstates > 256 || partial)) || force == 4) &&
-                         build_filter_image(h, trans, c->filter_rows_cap, &filter_img, &f_start, &f_m, &f_cend,
-                                            partial ? h.nstates - 1 : UINT32_MAX);
-  if ((force == 4 || partial) && !filter_ok) {
-    c->err = "dgrep_load_dfa: the filter stepper cannot hold this DFA's first states";
-    return DGREP_E_UNSUPPORTED;
-  }
-  if (pair_ok) {
-    c->step_kind = kStepPair;
-    c->nclasses = h.nclasses;
-    t.swap(pair_img);
-    start = pair_start;
-    start_m = pair_m;
-  } else if (filter_ok) {
-    c->step_kind = kStepFilter;
-    c->nclasses = h.nclasses;
-    c->cand_end = f_cend;
-    t.swap(filter_img);
-    start = f_start;
-    start_m = f_m;
-  }
-  c->loaded = false;  // the previous pattern's verification tables go now
-  ++c->load_gen;
-  if (c->d_nfa) HIPCHK(hipFree(c->d_nfa));
-  c->d_nfa = nullptr;
-  if (c->d_full) HIPCHK(hipFree(c->d_full));
-  c->d_full = nullptr;
-  if (c->d_ximg) HIPCHK(hipFree(c->d_ximg));
-  c->d_ximg = nullptr;
-  c->ximg_bytes = c->x_hot = c->x_rec = c->xr_off = 0;
-  if (pair_ok) {
-    // image built above
-  } else if (filter_ok && partial) {
-    const uint32_t* prog = trans + size_t(h.nstates) * h.nclasses;
-    if (h.nfa_bytes < 32 || prog[0] != DGREP_NFA_MAGIC || prog[1] > DGREP_NFA_MAX_POS) {
-      c->err = "dgrep_load_dfa: malformed NFA program";
-      return DGREP_E_INVALID;
-    }
-    c->nfa_words = prog[2];
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_nfa), h.nfa_bytes));
-    HIPCHK(hipMemcpy(c->d_nfa, prog, h.nfa_bytes, hipMemcpyHostToDevice));
-  } else if (filter_ok) {
-    // the whole DFA for verify_kernel, renumbered breadth-first from start
-    // (start, start_m, then BFS) so its hot rows lead; u16 entries while the
-    // ids fit, u32 above 65535 states (up to the compiler's budget)
-    const uint32_t S = h.nstates, K = h.nclasses;
-    std::vector<uint32_t> order, bid(S, UINT32_MAX);
-    order.reserve(S);
-    auto visit = [&](uint32_t x) {
-      if (bid[x] == UINT32_MAX) { bid[x] = uint32_t(order.size()); order.push_back(x); }
-    };
-    visit(h.start);
-    visit(h.start_m);
-    for (size_t q = 0; q < order.size(); ++q)
-      for (uint32_t k = 0; k < K; ++k) visit(trans[size_t(order[q]) * K + k]);
-    for (uint32_t x = 0; x < S; ++x) visit(x);
-    const size_t ne = size_t(S) * K;
-    c->full_u32 = S > 65535;
-    const size_t esz = c->full_u32 ? 4 : 2;
-    std::vector<uint8_t> full(ne * esz);
-    for (uint32_t n = 0; n < S; ++n)
-      for (uint32_t k = 0; k < K; ++k) {
-        const uint32_t x = bid[trans[size_t(order[n]) * K + k]];
-        if (c->full_u32) reinterpret_cast<uint32_t*>(full.data())[size_t(n) * K + k] = x;
-        else reinterpret_cast<uint16_t*>(full.data())[size_t(n) * K + k] = uint16_t(x);
-      }
-    HIPCHK(hipMalloc(&c->d_full, full.size()));
-    HIPCHK(hipMemcpy(c->d_full, full.data(), full.size(), hipMemcpyHostToDevice));
-    c->verify_hot = uint32_t(std::min<size_t>(ne, verify_hot_bytes() / esz)) / K * K;
-    std::vector<uint8_t> ximg;
-    if (!c->full_u32 &&
-        build_ximg(reinterpret_cast<const uint16_t*>(full.data()), S, K, long_dfa_lds_bytes(), &ximg, &c->x_hot,
-                   &c->xr_off)) {
-      c->x_rec = S - c->x_hot;
-      c->ximg_bytes = uint32_t(ximg.size());
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_ximg), ximg.size()));
-      HIPCHK(hipMemcpy(c->d_ximg, ximg.data(), ximg.size(), hipMemcpyHostToDevice));
-    }
-    if (!c->d_cls) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_cls), 256));
-    HIPCHK(hipMemcpy(c->d_cls, h.byte_class, 256, hipMemcpyHostToDevice));
-    c->blob_start = bid[h.start];
-    c->blob_start_m = bid[h.start_m];
-    // the absorbing states: MATCHED (every byte but '\n' loops, '\n' ->
-    // start_m; verification stops there) and DEAD (the same with '\n' ->
-    // start: a line there never matches)
-    c->blob_matched = c->blob_dead = UINT32_MAX;
-    const uint32_t cn = h.byte_class[uint8_t('\n')];
-    for (uint32_t x = 0; x < S; ++x) {
-      bool absorbing = true;
-      for (uint32_t k = 0; k < K && absorbing; ++k)
-        if (k != cn && trans[size_t(x) * K + k] != x) absorbing = false;
-      if (!absorbing) continue;
-      if (trans[size_t(x) * K + cn] == h.start_m && c->blob_matched == UINT32_MAX) c->blob_matched = bid[x];
-      if (trans[size_t(x) * K + cn] == h.start && c->blob_dead == UINT32_MAX) c->blob_dead = bid[x];
-    }
-    // long lines' lookback seeds: start, then states spread over the first
-    // breadth-first ids -- the rows the seg kernel holds in LDS, so a seed's
-    // first steps do not take the cold path -- never an absorbing one: a DFA
-    // keeping a finite memory of the whole line (a parity, a flag) has seeds
-    // in each memory class with high probability, so a segment's guesses cover
-    // its true entry state (long_c4p: 4.7 -> 485 GB/s)
-    const uint32_t NS = long_seeds();
-    const uint32_t H = std::min<uint32_t>(S, std::max<uint32_t>(
-                                                 64, c->x_hot ? c->x_hot : long_dfa_hot_bytes() / (esz * K)));
-    c->long_seed.assign(NS, c->blob_start);
-    for (uint32_t i = 1; i < NS && H > 2; ++i) {
-      uint32_t x = uint32_t(uint64_t(i) * (H - 1) / NS);
-      for (uint32_t t = 0; t < S && (x == c->blob_matched || x == c->blob_dead || x == c->blob_start); ++t)
-        x = (x + 1) % S;
-      c->long_seed[i] = x;
-    }
-  } else if (h.nstates > 256) {
-    // the filter holds any DFA's first states (build_filter_image): only its
-    // forced row cap (dgrep_set_stepper) can leave a large DFA here
-    c->err = "dgrep_load_dfa: a DFA of " + std::to_string(h.nstates) + " states needs the filter stepper";
-    return DGREP_E_UNSUPPORTED;
-  } else if (h.nstates <= DGREP_SHENG_MAX_STATES && force != 2) {
-    // StepSheng8: V[b] = 8 bytes, byte s = next state of s on input byte b
-    c->step_kind = kStepSheng8;
-    // renumber so start_m is the highest state (the kernel tests a word's four
-    // states for start_m with one max), and carry the start state replicated
-    // in all four bytes: v_perm keeps a replicated selector replicated, so
-    // every state on the chain is a clean 0x01010101 multiple
-    const uint32_t S = h.nstates, top = S - 1;
-    std::vector<uint32_t> id(S);
-    for (uint32_t x = 0; x < S; ++x) id[x] = x;
-    std::swap(id[h.start_m], id[top]);
-    t.assign(256 * 8, 0);
-    for (int b = 0; b < 256; ++b)
-      for (uint32_t s = 0; s < S; ++s)
-        t[size_t(b) * 8 + id[s]] = uint8_t(id[trans[size_t(s) * h.nclasses + h.byte_class[b]]]);
-    start = id[h.start] * 0x01010101u;
-    // V['\n'] for the long-line kernel (a line the split's end closes)
-    c->sheng_nl_lo = c->sheng_nl_hi = 0;
-    for (int k = 0; k < 4; ++k) {
-      c->sheng_nl_lo |= uint32_t(t[size_t('\n') * 8 + k]) << (8 * k);
-      c->sheng_nl_hi |= uint32_t(t[size_t('\n') * 8 + 4 + k]) << (8 * k);
-    }
-    start_m = top;
-    st2id.assign(S, 0);
-    for (uint32_t x = 0; x < S; ++x) st2id[id[x]] = x;
-  } else {
-    // StepTable: row s (stride scan_table_row() = 260, bank-staggered) holds
-    // trans[s][class(b)] at byte b
-    c->step_kind = kStepTable;
-    st2id.resize(h.nstates);
-    for (uint32_t x = 0; x < h.nstates; ++x) st2id[x] = x;
-    const size_t row = scan_table_row();
-    t.assign((size_t(h.nstates) * row + 15) & ~size_t(15), 0);
-    for (uint32_t s = 0; s < h.nstates; ++s)
-      for (int b = 0; b < 256; ++b) t[size_t(s) * row + size_t(b)] = uint8_t(trans[size_t(s) * h.nclasses + h.byte_class[b]]);
-  }
-  if (c->d_table) HIPCHK(hipFree(c->d_table));
-  c->d_table = nullptr;
-  c->table_bytes = uint32_t(t.size());
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_table), (t.size() + 15) & ~size_t(15)));
-  HIPCHK(hipMemcpy(c->d_table, t.data(), t.size(), hipMemcpyHostToDevice));
-  c->flags = h.flags;
-  c->nstates = h.nstates;
-  c->start = start;
-  c->start_m = start_m;
-  // long lines: the blob's u8 [S][256] table for the long-line kernels
-  if (c->d_long_tbl) HIPCHK(hipFree(c->d_long_tbl));
-  if (c->d_st2id) HIPCHK(hipFree(c->d_st2id));
-  c->d_long_tbl = nullptr;
-  c->d_st2id = nullptr;
-  c->long_states = 0;
-  if ((c->step_kind == kStepSheng8 || c->step_kind == kStepPair || c->step_kind == kStepTable) &&
-      h.nstates <= 256 &&
-      !st2id.empty()) {
-    std::vector<uint8_t> lt(size_t(h.nstates) * 256);
-    for (uint32_t s = 0; s < h.nstates; ++s)
-      for (int b = 0; b < 256; ++b) lt[size_t(s) * 256 + b] = uint8_t(trans[size_t(s) * h.nclasses + h.byte_class[b]]);
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_long_tbl), lt.size()));
-    HIPCHK(hipMemcpy(c->d_long_tbl, lt.data(), lt.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_st2id), st2id.size() * 4));
-    HIPCHK(hipMemcpy(c->d_st2id, st2id.data(), st2id.size() * 4, hipMemcpyHostToDevice));
-    c->long_states = h.nstates;
-    c->long_start_m = h.start_m;
-  }
-  c->empty_line_matches = trans[size_t(h.start) * h.nclasses + h.byte_class[uint8_t('\n')]] == h.start_m;
-  // the plain DFA for the carry walk: the device copy of the pattern before goes now
-  if (c->d_carry_trans) HIPCHK(hipFree(c->d_carry_trans));
-  if (c->d_carry_aux) HIPCHK(hipFree(c->d_carry_aux));
-  c->d_carry_trans = nullptr;
-  c->d_carry_aux = nullptr;
-  c->carry_ready = false;
-  c->h_trans.assign(trans, trans + size_t(h.nstates) * h.nclasses);
-  memcpy(c->h_cls, h.byte_class, 256);
-  c->h_nstates = h.nstates;
-  c->h_nclasses = h.nclasses;
-  c->h_start = h.start;
-  c->h_start_m = h.start_m;
+  PatternDevice d;
   int bpc = 0;
-  HIPCHK(scan_dfa_occupancy(launch_kind(c), c->table_bytes, &bpc));
+  hipError_t e = hipSetDevice(c->device);
+  if (e == hipSuccess) e = upload(img.table, &d.table);
+  if (e == hipSuccess) e = upload(img.full, &d.full);
+  if (e == hipSuccess && !img.full.empty()) e = upload(std::vector<uint8_t>(img.h_cls, img.h_cls + 256), &d.cls);
+  if (e == hipSuccess) e = upload(img.ximg, &d.ximg);
+  if (e == hipSuccess) e = upload(img.nfa, &d.nfa);
+  if (e == hipSuccess) e = upload(img.long_tbl, &d.long_tbl);
+  if (e == hipSuccess) e = upload(img.st2id, &d.st2id);
+  if (e == hipSuccess) e = scan_dfa_occupancy(launch_kind(img), img.table_bytes, &bpc);
+  if (e != hipSuccess) {
+    free_pattern_device(&d);
+    return hip_fail(c, e, "dgrep_load_dfa: upload");
+  }
+  free_pattern_device(&c->dev);  // the previous pattern goes now, its carry tables with it
+  c->dev = d;
+  c->pat = std::move(img);
+  c->pat.drop_uploaded();
   c->blocks_per_cu = std::max(1, std::min(bpc, DGREP_MAX_WG_PER_CU));
+  ++c->load_gen;
+  c->carry_ready = false;
   c->density = 0.0;
   c->staged_hint = 0;
   c->loaded = true;
@@ -911,10 +483,10 @@ static int resolve_long_lines(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, u
   la.chunk_nl = c->d_chunk_nl;
   la.pend = c->d_pend;
   la.npend = npend;
-  la.st2id = c->d_st2id;
-  la.tbl = c->d_long_tbl;
-  la.nstates = c->long_states;
-  la.start_m = c->long_start_m;
+  la.st2id = c->dev.st2id;
+  la.tbl = c->dev.long_tbl;
+  la.nstates = c->pat.long_states;
+  la.start_m = c->pat.long_start_m;
   HIPCHK(long_lines_end(la, c->stream));
   std::vector<PendingLine> P(npend);
   HIPCHK(hipMemcpyAsync(P.data(), c->d_pend, npend * sizeof(PendingLine), hipMemcpyDeviceToHost, c->stream));
@@ -1001,19 +573,19 @@ static int resolve_long_filter(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, 
   LongDfaArgs la;
   memset(&la, 0, sizeof la);
   la.data = d_data;
-  la.full = c->d_full;
-  la.hot_entries = c->verify_hot;
+  la.full = c->dev.full;
+  la.hot_entries = c->pat.verify_hot;
   {
-    const size_t esz = c->full_u32 ? 4 : 2, ne = size_t(c->nstates) * c->nclasses;
-    la.seg_hot_entries = uint32_t(std::min<size_t>(ne, long_dfa_hot_bytes() / esz)) / c->nclasses * c->nclasses;
+    const size_t esz = c->pat.full_u32 ? 4 : 2, ne = size_t(c->pat.nstates) * c->pat.nclasses;
+    la.seg_hot_entries = uint32_t(std::min<size_t>(ne, kLongDfaHotBytes / esz)) / c->pat.nclasses * c->pat.nclasses;
   }
-  la.nclasses = c->nclasses;
-  la.cls = c->d_cls;
-  la.start = c->blob_start;
-  la.start_m = c->blob_start_m;
-  la.matched = c->blob_matched;
-  la.dead = c->blob_dead;
-  for (uint32_t i = 0; i < long_seeds() && i < uint32_t(kLongSeeds); ++i) la.seed[i] = c->long_seed[i];
+  la.nclasses = c->pat.nclasses;
+  la.cls = c->dev.cls;
+  la.start = c->pat.blob_start;
+  la.start_m = c->pat.blob_start_m;
+  la.matched = c->pat.blob_matched;
+  la.dead = c->pat.blob_dead;
+  for (uint32_t i = 0; i < uint32_t(kLongSeeds); ++i) la.seed[i] = c->pat.long_seed[i];
   la.seg = c->d_seg;
   la.seg_from = c->d_seg_from;
   la.nseg = segs.size();
@@ -1022,13 +594,13 @@ static int resolve_long_filter(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, 
   la.seg_off = c->d_seg_off;
   la.pend = c->d_pend;
   la.npend = npend;
-  la.ximg = DGREP_LONG_XREC ? c->d_ximg : nullptr;
-  la.ximg_bytes = c->ximg_bytes;
-  la.x_hot = c->x_hot;
-  la.xr_off = c->xr_off;
+  la.ximg = DGREP_LONG_XREC ? c->dev.ximg : nullptr;
+  la.ximg_bytes = c->pat.ximg_bytes;
+  la.x_hot = c->pat.x_hot;
+  la.xr_off = c->pat.xr_off;
   // the fix kernel's tallies: two of the scan's counters, zeroed before the scan
   la.walk_count = c->d_counters + kCtrLongWalk;
-  HIPCHK(long_lines_dfa(la, c->full_u32, c->stream));
+  HIPCHK(long_lines_dfa(la, c->pat.full_u32, c->stream));
   unsigned long long walk[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(walk, la.walk_count, sizeof walk, hipMemcpyDeviceToHost, c->stream));
   // the host vectors are read by the async copies above: wait before they go
@@ -1045,12 +617,12 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
   *count = 0;
   dgrep_scan_stats& S = c->stats;
   S = dgrep_scan_stats{};
-  S.stepper = uint32_t(c->step_kind);
+  S.stepper = uint32_t(c->pat.step_kind);
   c->last_ms = 0.f;
-  if (c->flags & DGREP_DFA_MATCH_NONE) return DGREP_OK;
+  if (c->pat.flags & DGREP_DFA_MATCH_NONE) return DGREP_OK;
   if (n == 0) {
     // strings.Split("", "\n") == [""]: one empty line, line 1
-    if (!c->empty_line_matches) return DGREP_OK;
+    if (!c->pat.empty_line_matches) return DGREP_OK;
     *count = 1;
     S.matches = 1;
     if (capacity >= 1) {
@@ -1069,7 +641,7 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
   const uint64_t resident = uint64_t(c->num_cus) * uint64_t(c->blocks_per_cu);
   uint32_t chunk = 0, wpb = 1, slots = 0, threads = 0;
   bool spills = false;
-  const uint64_t tile = scan_tile_bytes(launch_kind(c), c->table_bytes, n, resident, c->lane_chunk, c->density,
+  const uint64_t tile = scan_tile_bytes(launch_kind(c->pat), c->pat.table_bytes, n, resident, c->lane_chunk, c->density,
                                         DGREP_SPILL_RECORDS, &chunk, &wpb, &slots, &threads, &spills);
   const uint64_t ntiles = (n + tile - 1) / tile;
   int rc;
@@ -1078,7 +650,7 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
   if ((rc = grow(c, &c->d_line_base, &c->lb_cap, ntiles + 1)) != DGREP_OK) return rc;
   // kStepFilter stages its candidates too: the staging buffer holds at least
   // the previous scan's staged lines, and grows (one re-scan) if they overflow
-  const bool filt = c->step_kind == kStepFilter && c->cand_end != UINT32_MAX;
+  const bool filt = c->pat.step_kind == kStepFilter && c->pat.cand_end != UINT32_MAX;
   if ((rc = grow(c, &c->d_staging, &c->staging_cap, filt ? std::max(capacity, c->staged_hint) : capacity)) != DGREP_OK)
     return rc;
 
@@ -1096,11 +668,11 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
   if ((rc = grow(c, &c->d_tails, &c->tails_cap, uint64_t(grid) * threads * streams)) != DGREP_OK) return rc;
   // the filter parks too when the whole DFA is at hand (not a partial blob, whose
   // candidates an NFA program decides: its lanes read a long line on)
-  const bool park_filter = DGREP_PARK && c->step_kind == kStepFilter && c->d_full != nullptr;
-  const bool park = (DGREP_PARK && c->d_long_tbl != nullptr) || park_filter;
+  const bool park_filter = DGREP_PARK && c->pat.step_kind == kStepFilter && c->dev.full != nullptr;
+  const bool park = (DGREP_PARK && c->dev.long_tbl != nullptr) || park_filter;
   const uint64_t nchunks = (n + chunk - 1) / chunk;
   // Sheng: the chunk maps replace the '\n' counts (long_sheng_kernel)
-  const bool park_maps = park && c->step_kind == kStepSheng8 && DGREP_SHENG_MAPS;
+  const bool park_maps = park && c->pat.step_kind == kStepSheng8 && DGREP_SHENG_MAPS;
   if (park) {
     if (park_maps) {
       if ((rc = grow(c, &c->d_chunk_map, &c->chunk_map_cap, nchunks)) != DGREP_OK) return rc;
@@ -1114,10 +686,10 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
   memset(&a, 0, sizeof a);
   a.data = d_data;
   a.n = n;
-  a.table = c->d_table;
-  a.table_bytes = c->table_bytes;
-  a.start = c->start;
-  a.start_m = c->start_m;
+  a.table = c->dev.table;
+  a.table_bytes = c->pat.table_bytes;
+  a.start = c->pat.start;
+  a.start_m = c->pat.start_m;
   a.chunk = chunk;
   a.ntiles = ntiles;
   a.counter = c->d_counters;
@@ -1128,11 +700,11 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
   a.tails = c->d_tails;
   a.chunk_nl = park && !park_maps ? c->d_chunk_nl : nullptr;
   a.chunk_map = park_maps ? c->d_chunk_map : nullptr;
-  a.nclasses = c->nclasses;
-  a.pair_t1 = c->pair_args.t1;
-  a.pair_thr = c->pair_args.thr;
-  a.pair_div = c->pair_args.div;
-  a.cand_end = c->cand_end;
+  a.nclasses = c->pat.nclasses;
+  a.pair_t1 = c->pat.pair_args.t1;
+  a.pair_thr = c->pat.pair_args.thr;
+  a.pair_div = c->pat.pair_args.div;
+  a.cand_end = c->pat.cand_end;
   a.spill = use_spill ? c->d_spill : nullptr;
   a.spill_per_lane = use_spill ? DGREP_SPILL_RECORDS : 0;
   // every resident workgroup is launched even when the last round of tiles is
@@ -1166,7 +738,7 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
     a.pend_cap = park ? c->pend_cap : 0;
     HIPCHK(hipMemsetAsync(c->d_counters, 0, kCounters * sizeof(unsigned long long), c->stream));
     HIPCHK(hipEventRecord(c->ev0, c->stream));
-    HIPCHK(scan_dfa(launch_kind(c), a, grid, c->stream));
+    HIPCHK(scan_dfa(launch_kind(c->pat), a, grid, c->stream));
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     // (the kernel reads the counters itself and leaves the arrays alone if a
     // lane overflowed or a line was parked: entries [count, capacity) are never
@@ -1228,7 +800,7 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
   const bool over = ctr[1] && staged <= a.capacity;
   if (over) {
     HIPCHK(hipEventRecord(c->ev2, c->stream));
-    HIPCHK(scan_dfa_overflow(launch_kind(c), a, ctr[1], c->stream));
+    HIPCHK(scan_dfa_overflow(launch_kind(c->pat), a, ctr[1], c->stream));
     HIPCHK(hipEventRecord(c->ev3, c->stream));
   }
   uint64_t total = staged;
@@ -1239,26 +811,26 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
     VerifyArgs v;
     memset(&v, 0, sizeof v);
     v.data = d_data;
-    v.full = c->d_full;
-    v.full_u32 = c->full_u32 ? 1u : 0u;
-    v.hot_entries = c->verify_hot;
-    v.cls = c->d_cls;
-    v.nclasses = c->nclasses;
-    v.start = c->blob_start;
-    v.start_m = c->blob_start_m;
+    v.full = c->dev.full;
+    v.full_u32 = c->pat.full_u32 ? 1u : 0u;
+    v.hot_entries = c->pat.verify_hot;
+    v.cls = c->dev.cls;
+    v.nclasses = c->pat.nclasses;
+    v.start = c->pat.blob_start;
+    v.start_m = c->pat.blob_start_m;
     v.tiles = c->d_tiles;
     v.ntiles = ntiles;
     v.staging = c->d_staging;
     v.staging_cap = c->staging_cap;
     v.removed = c->d_counters + 3;  // zeroed before the scan
-    v.nfa = c->d_nfa;
-    v.nfa_words = c->nfa_words;
-    v.matched = c->d_nfa ? UINT32_MAX : c->blob_matched;
+    v.nfa = c->dev.nfa;
+    v.nfa_words = c->pat.nfa_words;
+    v.matched = c->dev.nfa ? UINT32_MAX : c->pat.blob_matched;
     v.pend = c->d_pend;
-    v.ximg = DGREP_VERIFY_XREC ? c->d_ximg : nullptr;
-    v.ximg_bytes = c->ximg_bytes;
-    v.x_hot = c->x_hot;
-    v.xr_off = c->xr_off;
+    v.ximg = DGREP_VERIFY_XREC ? c->dev.ximg : nullptr;
+    v.ximg_bytes = c->pat.ximg_bytes;
+    v.x_hot = c->pat.x_hot;
+    v.xr_off = c->pat.xr_off;
     v.num_cus = uint32_t(c->num_cus);
     HIPCHK(hipEventRecord(c->ev4, c->stream));
     if (npend && park_maps) {
@@ -1270,10 +842,10 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
       la.pend = c->d_pend;
       la.npend = npend;
       la.chunk_map = c->d_chunk_map;
-      la.sheng_m = c->start_m;
-      la.nl_lo = c->sheng_nl_lo;
-      la.nl_hi = c->sheng_nl_hi;
-      la.sheng_v = reinterpret_cast<const uint2*>(c->d_table);
+      la.sheng_m = c->pat.start_m;
+      la.nl_lo = c->pat.sheng_nl_lo;
+      la.nl_hi = c->pat.sheng_nl_hi;
+      la.sheng_v = reinterpret_cast<const uint2*>(c->dev.table);
       la.data = d_data;
       HIPCHK(long_lines_sheng(la, c->stream));
     } else if (npend && park_filter) {
@@ -1314,10 +886,10 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
       la.pend = c->d_pend;
       la.npend = npend;
       la.chunk_map = c->d_chunk_map;
-      la.sheng_m = c->start_m;
-      la.nl_lo = c->sheng_nl_lo;
-      la.nl_hi = c->sheng_nl_hi;
-      la.sheng_v = reinterpret_cast<const uint2*>(c->d_table);
+      la.sheng_m = c->pat.start_m;
+      la.nl_lo = c->pat.sheng_nl_lo;
+      la.nl_hi = c->pat.sheng_nl_hi;
+      la.sheng_v = reinterpret_cast<const uint2*>(c->dev.table);
       la.data = d_data;
       HIPCHK(long_lines_sheng(la, c->stream));
     } else if ((rc = park_filter ? resolve_long_filter(c, d_data, n, chunk, nchunks, npend)
@@ -1570,7 +1142,7 @@ static int batch_resident(dgrep_ctx* c, const uint8_t* d_packed, uint64_t n, uin
   if ((rc = scan_resident(c, d_packed, n, d_line, d_start, d_len, capacity, count)) != DGREP_OK) return rc;
   if (prepass) {
     // scan_resident waited for the stream unless it had nothing to scan
-    if (n == 0 || (c->flags & DGREP_DFA_MATCH_NONE)) HIPCHK(hipStreamSynchronize(c->stream));
+    if (n == 0 || (c->pat.flags & DGREP_DFA_MATCH_NONE)) HIPCHK(hipStreamSynchronize(c->stream));
     if (*c->h_bat_flag != UINT64_MAX) {
       c->err = "packed buffer: the byte after split " + std::to_string(*c->h_bat_flag) + " is not '\\n'";
       *count = 0;
@@ -1900,7 +1472,7 @@ static uint32_t sat_add32(uint32_t a, uint32_t b) { return uint32_t(std::min<uin
 
 static void win_stats_begin(dgrep_stream* s) {
   s->agg = dgrep_scan_stats{};
-  s->agg.stepper = uint32_t(s->c->step_kind);
+  s->agg.stepper = uint32_t(s->c->pat.step_kind);
   s->agg_ms = 0.f;
   s->call_encode_ms = 0.f;
 }
@@ -2034,37 +1606,37 @@ static int win_acc_reserve(dgrep_stream* s, uint64_t need) {
 // dgrep_load_dfa kept: once per pattern, at the first fold.
 static int carry_ensure(dgrep_ctx* c) {
   if (c->carry_ready) return DGREP_OK;
-  const uint32_t S = c->h_nstates, K = c->h_nclasses, nl = c->h_cls[uint8_t('\n')];
+  const uint32_t S = c->pat.h_nstates, K = c->pat.h_nclasses, nl = c->pat.h_cls[uint8_t('\n')];
   const size_t ne = size_t(S) * K;
   const bool u32 = S > 65535;
-  const std::vector<uint8_t> absorbing = carry_absorbing(c->h_trans.data(), S, K, nl);
+  const std::vector<uint8_t> absorbing = carry_absorbing(c->pat.h_trans.data(), S, K, nl);
   std::vector<uint8_t> aux(256 + size_t(S));
-  memcpy(aux.data(), c->h_cls, 256);
+  memcpy(aux.data(), c->pat.h_cls, 256);
   memcpy(aux.data() + 256, absorbing.data(), S);
   std::vector<uint16_t> t16;
-  const void* src = c->h_trans.data();
+  const void* src = c->pat.h_trans.data();
   size_t bytes = ne * 4;
   if (!u32) {
     t16.resize(ne);
-    for (size_t i = 0; i < ne; ++i) t16[i] = uint16_t(c->h_trans[i]);
+    for (size_t i = 0; i < ne; ++i) t16[i] = uint16_t(c->pat.h_trans[i]);
     src = t16.data();
     bytes = ne * 2;
   }
-  if (!c->d_carry_trans) HIPCHK(hipMalloc(&c->d_carry_trans, std::max<size_t>(bytes, 16)));
-  if (!c->d_carry_aux) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_carry_aux), aux.size()));
-  HIPCHK(hipMemcpy(c->d_carry_trans, src, bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(c->d_carry_aux, aux.data(), aux.size(), hipMemcpyHostToDevice));
+  if (!c->dev.carry_trans) HIPCHK(hipMalloc(&c->dev.carry_trans, std::max<size_t>(bytes, 16)));
+  if (!c->dev.carry_aux) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->dev.carry_aux), aux.size()));
+  HIPCHK(hipMemcpy(c->dev.carry_trans, src, bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(c->dev.carry_aux, aux.data(), aux.size(), hipMemcpyHostToDevice));
   CarryTable& t = c->carry;
-  t.trans = c->d_carry_trans;
-  t.cls = c->d_carry_aux;
-  t.absorbing = c->d_carry_aux + 256;
+  t.trans = c->dev.carry_trans;
+  t.cls = c->dev.carry_aux;
+  t.absorbing = c->dev.carry_aux + 256;
   t.nstates = S;
   t.nclasses = K;
-  t.start = c->h_start;
-  t.start_m = c->h_start_m;
+  t.start = c->pat.h_start;
+  t.start_m = c->pat.h_start_m;
   t.nl_class = nl;
   t.u32 = u32;
-  carry_seeds(absorbing, S, c->h_start, t.seed);
+  carry_seeds(absorbing, S, c->pat.h_start, t.seed);
   c->carry_ready = true;
   return DGREP_OK;
 }
@@ -2092,7 +1664,7 @@ static int win_walk(dgrep_stream* s, const uint8_t* d, uint64_t m, bool want_ver
     HIPCHK(hipEventSynchronize(s->ev_w1));
     if ((rc = carry_ms_take(s)) != DGREP_OK) return rc;
   }
-  const bool rows_in_lds = uint64_t(c->h_nstates) * c->h_nclasses * (c->carry.u32 ? 4 : 2) <= kCarryRowsLds;
+  const bool rows_in_lds = uint64_t(c->pat.h_nstates) * c->pat.h_nclasses * (c->carry.u32 ? 4 : 2) <= kCarryRowsLds;
   const CarryPlan plan = carry_plan(m, carry_lanes(m, uint64_t(std::max(c->num_cus, 1)), rows_in_lds));
   if ((rc = grow(c, &s->d_pairs, &s->pairs_cap, carry_pairs_bytes(plan) / 4)) != DGREP_OK) return rc;
   CarryWalk w;
@@ -2561,7 +2133,7 @@ extern "C" int dgrep_stream_open(dgrep_ctx* c, size_t window_bytes, uint32_t fla
     return DGREP_E_INVALID;
   }
   if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
-  if (bounded && (c->flags & DGREP_DFA_PARTIAL)) {
+  if (bounded && (c->pat.flags & DGREP_DFA_PARTIAL)) {
     c->err = kBoundedPartial;
     return DGREP_E_UNSUPPORTED;
   }
@@ -2616,7 +2188,7 @@ extern "C" int dgrep_stream_feed(dgrep_stream* s, const uint8_t* data, size_t n,
   int rc;
   if ((rc = win_enter(s, true)) != DGREP_OK) return rc;
   win_stats_begin(s);
-  if (n && !(c->flags & DGREP_DFA_MATCH_NONE)) {
+  if (n && !(c->pat.flags & DGREP_DFA_MATCH_NONE)) {
     HIPCHK(hipSetDevice(c->device));
     if ((rc = win_fail(s, win_feed(s, data, n))) != DGREP_OK) return rc;
     if ((rc = win_fail(s, win_collect(s, out))) != DGREP_OK) return rc;
@@ -2635,7 +2207,7 @@ extern "C" int dgrep_stream_finish(dgrep_stream* s, dgrep_stream_result* out) {
   int rc;
   if ((rc = win_enter(s, false)) != DGREP_OK) return rc;
   win_stats_begin(s);
-  if (!(c->flags & DGREP_DFA_MATCH_NONE)) {
+  if (!(c->pat.flags & DGREP_DFA_MATCH_NONE)) {
     HIPCHK(hipSetDevice(c->device));
     if ((rc = win_fail(s, win_finish(s))) != DGREP_OK) return rc;
     if ((rc = win_fail(s, win_collect(s, out))) != DGREP_OK) return rc;
@@ -2701,7 +2273,7 @@ static int scan_windowed_flags(dgrep_ctx* c, const uint8_t* data, size_t n, size
     return DGREP_E_INVALID;
   }
   if (!c->loaded) { c->err = "no DFA loaded"; return DGREP_E_NO_DFA; }
-  if ((flags & DGREP_STREAM_BOUNDED) && (c->flags & DGREP_DFA_PARTIAL)) {
+  if ((flags & DGREP_STREAM_BOUNDED) && (c->pat.flags & DGREP_DFA_PARTIAL)) {
     c->err = kBoundedPartial;
     return DGREP_E_UNSUPPORTED;
   }
@@ -2711,7 +2283,7 @@ static int scan_windowed_flags(dgrep_ctx* c, const uint8_t* data, size_t n, size
   dgrep_stream_result r;
   memset(&r, 0, sizeof r);
   win_stats_begin(s);
-  if (rc == DGREP_OK && !(c->flags & DGREP_DFA_MATCH_NONE)) {
+  if (rc == DGREP_OK && !(c->pat.flags & DGREP_DFA_MATCH_NONE)) {
     if (n) rc = win_fail(s, win_feed(s, data, n));
     if (rc == DGREP_OK) rc = win_fail(s, win_finish(s));
     if (rc == DGREP_OK) rc = win_fail(s, win_collect(s, &r));
@@ -2816,7 +2388,7 @@ extern "C" int dgrep_stream_feed_partitions(dgrep_stream* s, const uint8_t* data
   int rc;
   if ((rc = win_enter(s, true)) != DGREP_OK) return rc;
   win_stats_begin(s);
-  if (n && !(c->flags & DGREP_DFA_MATCH_NONE)) {
+  if (n && !(c->pat.flags & DGREP_DFA_MATCH_NONE)) {
     HIPCHK(hipSetDevice(c->device));
     if ((rc = win_fail(s, win_feed(s, data, n))) != DGREP_OK) return rc;
     if ((rc = win_fail(s, win_collect_parts(s, out))) != DGREP_OK) return rc;
@@ -2835,7 +2407,7 @@ extern "C" int dgrep_stream_finish_partitions(dgrep_stream* s, dgrep_batch_parti
   int rc;
   if ((rc = win_enter(s, false)) != DGREP_OK) return rc;
   win_stats_begin(s);
-  if (!(c->flags & DGREP_DFA_MATCH_NONE)) {
+  if (!(c->pat.flags & DGREP_DFA_MATCH_NONE)) {
     HIPCHK(hipSetDevice(c->device));
     if ((rc = win_fail(s, win_finish(s))) != DGREP_OK) return rc;
     if ((rc = win_fail(s, win_collect_parts(s, out))) != DGREP_OK) return rc;
@@ -2865,9 +2437,9 @@ extern "C" int dgrep_map_partitions_windowed(dgrep_ctx* c, const uint8_t* data, 
   if (!c || !out || (n && !data)) return DGREP_E_INVALID;
   int rc;
   if ((rc = parts_args_ok(c, window_bytes, filename, fn, nreduce)) != DGREP_OK) return rc;
-  if (c->flags & DGREP_DFA_MATCH_NONE) {
+  if (c->pat.flags & DGREP_DFA_MATCH_NONE) {
     c->stats = dgrep_scan_stats{};
-    c->stats.stepper = uint32_t(c->step_kind);
+    c->stats.stepper = uint32_t(c->pat.step_kind);
     c->last_ms = c->last_encode_ms = 0.f;
     return parts_empty(nreduce, out);
   }
@@ -3614,7 +3186,7 @@ static int job_flush(dgrep_job* j) {
   dgrep_ctx* c = j->c;
   uint64_t bytes = 0;
   const uint64_t k = job_pack_flush(&j->plan, &bytes);
-  if (k == 0 || (c->flags & DGREP_DFA_MATCH_NONE)) return DGREP_OK;  // (no line can match: the plan's tallies only)
+  if (k == 0 || (c->pat.flags & DGREP_DFA_MATCH_NONE)) return DGREP_OK;  // (no line can match: the plan's tallies only)
   std::vector<const uint8_t*> data(k);
   std::vector<const char*> fname(k);
   std::vector<size_t> fn(k);
@@ -3780,7 +3352,7 @@ extern "C" int dgrep_job_add(dgrep_job* j, const uint8_t* data, size_t n, const 
   if ((rc = job_enter(j, "dgrep_job_add")) != DGREP_OK) return rc;
   if (j->in_file) { c->err = "dgrep_job_add inside a file: dgrep_job_file_end comes first"; return DGREP_E_INVALID; }
   const JobStep step = job_next_file(&j->plan, n, false);
-  if (c->flags & DGREP_DFA_MATCH_NONE) {  // no line can match: the file is routed and counted, nothing is copied
+  if (c->pat.flags & DGREP_DFA_MATCH_NONE) {  // no line can match: the file is routed and counted, nothing is copied
     if (step.flush_first) (void)job_flush(j);
     if (step.route == kJobRoutePack) job_pack_push(&j->plan, n);
     return DGREP_OK;
@@ -3834,7 +3406,7 @@ extern "C" int dgrep_job_file_begin(dgrep_job* j, const char* filename, size_t f
   if (j->in_file) { c->err = "dgrep_job_file_begin inside a file: dgrep_job_file_end comes first"; return DGREP_E_INVALID; }
   j->in_file = true;
   const JobStep step = job_next_file(&j->plan, 0, true);
-  if (c->flags & DGREP_DFA_MATCH_NONE) {
+  if (c->pat.flags & DGREP_DFA_MATCH_NONE) {
     if (step.flush_first) (void)job_flush(j);
     return DGREP_OK;
   }
@@ -3848,7 +3420,7 @@ extern "C" int dgrep_job_file_feed(dgrep_job* j, const uint8_t* data, size_t n) 
   int rc;
   if ((rc = job_enter(j, "dgrep_job_file_feed")) != DGREP_OK) return rc;
   if (!j->in_file) { c->err = "dgrep_job_file_feed without dgrep_job_file_begin"; return DGREP_E_INVALID; }
-  if (n == 0 || (c->flags & DGREP_DFA_MATCH_NONE)) return DGREP_OK;
+  if (n == 0 || (c->pat.flags & DGREP_DFA_MATCH_NONE)) return DGREP_OK;
   HIPCHK(hipSetDevice(c->device));
   return job_fail(j, win_feed(j->s, data, n));
 }
@@ -3860,7 +3432,7 @@ extern "C" int dgrep_job_file_end(dgrep_job* j) {
   if ((rc = job_enter(j, "dgrep_job_file_end")) != DGREP_OK) return rc;
   if (!j->in_file) { c->err = "dgrep_job_file_end without dgrep_job_file_begin"; return DGREP_E_INVALID; }
   j->in_file = false;
-  if (c->flags & DGREP_DFA_MATCH_NONE) return DGREP_OK;
+  if (c->pat.flags & DGREP_DFA_MATCH_NONE) return DGREP_OK;
   HIPCHK(hipSetDevice(c->device));
   return job_fail(j, win_finish(j->s));
 }

@@ -110,6 +110,17 @@ const char* dgrep_last_error(dgrep_ctx* ctx);
 /* Use an existing hipStream_t (e.g. torch.cuda.current_stream().cuda_stream);
  * NULL selects the context's own stream. */
 int dgrep_set_stream(dgrep_ctx* ctx, void* hip_stream);
+/* Loads a compiled pattern: builds its images on the host
+ * (csrc/runtime/pattern_image.h, build_pattern_image: the stepper choice and
+ * every table; constants in csrc/kernels/pattern_layout.h and
+ * scan_common.h), uploads them into fresh device allocations, then commits.
+ * Failure rule: a refusal found on the host -- DGREP_E_INVALID (malformed
+ * blob), DGREP_E_UNSUPPORTED (the stepper dgrep_set_stepper forces cannot run
+ * this DFA) -- leaves the context exactly as it was: a previously loaded
+ * pattern stays loaded and usable, and streams and jobs opened under it stay
+ * valid. A HIP failure during the upload (DGREP_E_HIP) frees what the call
+ * allocated and leaves the previous pattern as well. Only a successful load
+ * replaces the pattern and invalidates the streams and jobs opened before. */
 int dgrep_load_dfa(dgrep_ctx* ctx, const void* blob, size_t n);
 /* Stepper selection for later dgrep_load_dfa calls (tests / tuning only; the
  * default picks by size: <= 8 states Sheng; else the pair stepper if its

@@ -114,3 +114,54 @@ def test_table_refuses_257_states_and_the_context_stays_usable(gpu_ctx):
         assert ctx.scan_stats()["stepper"] == "pair"
     finally:
         ctx.set_stepper("auto")
+
+
+def test_a_refused_load_leaves_the_loaded_pattern_whole(gpu_ctx):
+    """dgrep_load_dfa's failure rule (dgrep.h): a refusal found on the host
+    leaves the context exactly as it was. pair-9 stays loaded through three
+    refusals -- a pair table that does not fit, a filter of 3 rows, and a row
+    cap that leaves a 257-state DFA without a stepper -- its scan gives the same
+    lines after each, and a stream opened before them still feeds."""
+    import dgrep
+
+    ctx = gpu_ctx
+    cells = {c.name: c for c in SC.CELLS}
+    pair9 = cells["pair-9"]
+    try:
+        ctx.set_stepper("auto")
+        ctx.load(pair9.pattern)
+        data = bytes(SC.pad(4096 - len(pair9.hit) - 1, pair9)) + pair9.hit + b"\n"
+        for at in (100, 1500, 3000):
+            data = data[:at] + b"\n" + pair9.hit + b"\n" + data[at + len(pair9.hit) + 2:]
+        assert len(data) == 4096
+        want = O.grep_map(pair9.pattern, data)
+        assert len(want[0]) >= 4
+
+        def check():
+            got = ctx.scan(data)
+            for g, w in zip(got, want):
+                np.testing.assert_array_equal(g, w)
+            assert ctx.scan_stats()["stepper"] == "pair"
+
+        check()
+        half = len(data) // 2
+        with ctx.stream(1 << 16) as s:
+            first = s.feed(data[:half])
+            attempts = (
+                ("pair", 0, cells["table-auto-32"],
+                 "dgrep_load_dfa: the pair stepper's two-byte table does not fit this DFA"),
+                ("filter", 3, pair9, "dgrep_load_dfa: the filter stepper cannot hold this DFA's first states"),
+                ("auto", 3, cells["filter-257"], "dgrep_load_dfa: a DFA of 257 states needs the filter stepper"),
+            )
+            for force, rows, cell, message in attempts:
+                ctx.set_stepper(force, rows)
+                with pytest.raises(dgrep.UnsupportedPattern) as e:
+                    ctx.load(cell.pattern)
+                assert e.value.code == dgrep.DGREP_E_UNSUPPORTED and str(e.value).endswith(": " + message), e.value
+                check()
+            rest = [s.feed(data[half:]), s.finish()]
+            got = [np.concatenate([first[k]] + [r[k] for r in rest]) for k in range(3)]
+            for g, w in zip(got, want):
+                np.testing.assert_array_equal(g, w)
+    finally:
+        ctx.set_stepper("auto")

@@ -1,7 +1,7 @@
 """CPU model of how the filter stepper's parked lines are decided on the whole
 DFA (long_dfa_seg1_kernel / long_dfa_fix_kernel in csrc/kernels/scan_dfa.hip,
-the seeds of dgrep_load_dfa and the segment cut of resolve_long_filter in
-csrc/runtime/dgrep_runtime.hip).
+the seeds of long_seeds in csrc/runtime/pattern_image.h and the segment cut of
+resolve_long_filter in csrc/runtime/dgrep_runtime.hip).
 
 A parked line is cut into 16 KiB segments. Each segment but the first is run
 from up to 4 GUESSED entry states: 8 seed states (start, then states spread

@@ -1,13 +1,14 @@
 """CPU emulation of the pair stepper's algorithm (StepPair in
 csrc/kernels/scan_dfa.hip, image built by build_pair_image in
-csrc/runtime/dgrep_runtime.hip): two input bytes per table lookup, with
+csrc/runtime/pattern_image.h): two input bytes per table lookup, with
 SHADOW states carrying the event of a '\\n' that is the first byte of a pair.
 
 The emulation restates the construction (ids, premultiplied rows, shadow
 targets, the >= thr / >= M event rule) in numpy and steps whole splits pair by
 pair from offset 0, then compares the matching line numbers with the oracle's
-restatement of grep.go Map. The GPU parity tests check the C++ builder and the
-kernel; this pins the algorithm itself, CPU only."""
+restatement of grep.go Map. The GPU parity tests check the kernel and
+tests/test_pattern_image.py the C++ builder; this pins the algorithm itself,
+CPU only."""
 import random
 import zlib
 

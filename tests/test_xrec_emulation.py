@@ -1,6 +1,6 @@
 """CPU emulation of the default-row records of long_dfa_seg_kernel (DfaXRec in
-csrc/kernels/scan_common.h, built by build_ximg in
-csrc/runtime/dgrep_runtime.hip, read by FullDfa::next in
+csrc/kernels/pattern_layout.h, built by build_ximg in
+csrc/runtime/pattern_image.h, read by FullDfa::next in
 csrc/kernels/scan_dfa.hip).
 
 A u16 DFA's first H breadth-first rows sit in LDS whole; each further state
@@ -10,7 +10,8 @@ exceptions; a state no resident row comes within two classes of gets an extra
 row of its own as default (build_ximg). The emulation restates the construction in numpy and checks that
 the record lookup reproduces every entry of the table, for the configs'
 keyword automaton and a few other filter-sized patterns. The GPU long-line
-tests (tests/test_gpu_long_lines.py) check the C++ builder and the kernel."""
+tests (tests/test_gpu_long_lines.py) check the kernel; tests/test_pattern_image.py
+checks the C++ builder on the CPU."""
 import collections
 
 import numpy as np

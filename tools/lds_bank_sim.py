@@ -2,7 +2,7 @@
 
 Replays what a wave's 64 lanes read from LDS while stepping a corpus with the
 pair stepper (StepPair in csrc/kernels/scan_dfa.hip, image of build_pair_image
-in csrc/runtime/dgrep_runtime.hip): per word the four byte-table reads
+in csrc/runtime/pattern_image.h): per word the four byte-table reads
 (UA[b0], UB[b1], UA[b2], UB[b3]) and the two dependent T2 reads. A wave64
 ds_read_b32 / ds_read_u16 is served as two 32-lane groups; a group takes as
 many LDS cycles as the most distinct dwords any one bank ((a/4) mod 32) holds

@@ -3,7 +3,7 @@
 Replays the dependent ds_read_u16 of StepFilter (csrc/kernels/scan_dfa.hip)
 for a wave's 64 lanes stepping config 4's corpus (synth kind 1, seed 4) with
 its 1,000-keyword (?i) DFA, the filter image of build_filter_image
-(csrc/runtime/dgrep_runtime.hip: breadth-first rows from start, CAND for the
+(csrc/runtime/pattern_image.h: breadth-first rows from start, CAND for the
 rest), and scores row layouts the same way tools/lds_bank_sim.py does for the
 pair stepper: a wave64 u16 read is two 32-lane groups, each taking as many LDS
 cycles as the most distinct dwords one bank ((a/4) mod 32) holds
