@@ -31,6 +31,8 @@
 #include "../kernels/scan_common.h"
 #include "../kernels/synth.h"
 #include "../kernels/window.h"
+#include "device_buf.h"
+#include "ingest.h"
 #include "job_plan.h"
 #include "pack_pieces.h"
 #include "pattern_image.h"
@@ -118,7 +120,7 @@ static void free_pattern_device(PatternDevice* d) {
 struct dgrep_ctx {
   int device = 0;
   int num_cus = 0;
-  hipStream_t own_stream = nullptr;
+  Stream own_stream;  // before every buffer and event: destroyed after them
   hipStream_t stream = nullptr;
   std::string err;
 
@@ -136,49 +138,31 @@ struct dgrep_ctx {
   uint32_t lane_chunk = 0;  // dgrep_set_lane_chunk (0 = adaptive)
 
   // per-scan scratch (grown on demand, reused)
-  TileInfo* d_tiles = nullptr;
-  uint64_t* d_out_off = nullptr;
-  uint64_t* d_line_base = nullptr;
-  uint64_t tiles_cap = 0, off_cap = 0, lb_cap = 0;
-  StagedLine* d_staging = nullptr;
-  uint64_t staging_cap = 0;
+  DevBuf<TileInfo> d_tiles;
+  DevBuf<uint64_t> d_out_off, d_line_base;
+  DevBuf<StagedLine> d_staging;
   // device counters: [0] staging append counter, [1] overflow lanes, [2] parked
   // lines, [3] dropped candidates, [4] claimed tiles
-  unsigned long long* d_counters = nullptr;
-  OverflowLane* d_overflow = nullptr;
-  uint64_t overflow_cap = 0;
-  uint2* d_spill = nullptr;  // HBM spill areas of the resident threads (ScanArgs::spill)
-  uint64_t spill_cap = 0;
-  uint64_t* d_tails = nullptr;     // ScanArgs::tails (resident threads x streams)
-  uint64_t tails_cap = 0;
-  uint32_t* d_chunk_nl = nullptr;  // '\n' per chunk (ScanArgs::chunk_nl)
-  uint64_t chunk_nl_cap = 0;
-  ChunkMap* d_chunk_map = nullptr;  // Sheng: per-chunk maps (ScanArgs::chunk_map)
-  uint64_t chunk_map_cap = 0;
-  PendingLine* d_pend = nullptr;   // parked long lines
-  uint64_t pend_cap = 0;
+  DevBuf<unsigned long long> d_counters;
+  DevBuf<OverflowLane> d_overflow;
+  DevBuf<uint2> d_spill;            // HBM spill areas of the resident threads (ScanArgs::spill)
+  DevBuf<uint64_t> d_tails;         // ScanArgs::tails (resident threads x streams)
+  DevBuf<uint32_t> d_chunk_nl;      // '\n' per chunk (ScanArgs::chunk_nl)
+  DevBuf<ChunkMap> d_chunk_map;     // Sheng: per-chunk maps (ScanArgs::chunk_map)
+  DevBuf<PendingLine> d_pend;       // parked long lines
   // long lines (dev.long_tbl / dev.st2id on the Sheng, pair and table steppers)
-  LongSeg* d_seg = nullptr;
-  uint64_t seg_cap = 0;
-  uint64_t* d_seg_off = nullptr;
-  uint64_t seg_off_cap = 0;
-  uint8_t* d_segmap = nullptr;
-  uint64_t segmap_cap = 0;
+  DevBuf<LongSeg> d_seg;
+  DevBuf<uint64_t> d_seg_off;
+  DevBuf<uint8_t> d_segmap;
   // filter stepper: parked lines on the whole DFA (long_dfa_* kernels)
-  uint64_t* d_seg_from = nullptr;
-  uint64_t seg_from_cap = 0;
-  uint32_t* d_seg_state = nullptr;  // [2][guesses][nseg]: guesses, exits
-  uint64_t seg_state_cap = 0;
+  DevBuf<uint64_t> d_seg_from;
+  DevBuf<uint32_t> d_seg_state;  // [2][guesses][nseg]: guesses, exits
 
   // dgrep_scan (host data) buffers
-  uint8_t* d_data = nullptr;
-  size_t data_cap = 0;
-  uint64_t* d_res_line = nullptr;
-  uint64_t* d_res_start = nullptr;
-  uint64_t* d_res_len = nullptr;
-  uint64_t res_cap = 0;
+  DevBuf<uint8_t> d_data;
+  DevBuf<uint64_t> d_res_line, d_res_start, d_res_len;  // grown together (grow_results)
 
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr, ev4 = nullptr, ev5 = nullptr;
+  Event ev0, ev1, ev2, ev3, ev4, ev5;
   uint64_t staged_hint = 0;  // kStepFilter: staged lines (candidates included) of the last scan
   float last_ms = 0.f;
   double ms_sum = 0.0;  // last_ms summed over the dgrep_scan_device calls since dgrep_take_kernel_ms
@@ -188,65 +172,39 @@ struct dgrep_ctx {
   // dgrep_load_dfa): caps the adaptive lane chunk (scan_tile_bytes)
   double density = 0.0;
 
-  // dgrep_scan ingest (worker split -> HBM): host bytes are copied by
-  // `ingest_threads` CPU threads into one of `ingest_bufs` pinned staging
-  // buffers of `ingest_chunk` bytes while the copy engine DMAs the previous
-  // one to HBM on `copy_stream` (dgrep_set_ingest; chunk 0 = one direct
-  // pageable hipMemcpyAsync)
-  size_t ingest_chunk = size_t(64) << 20;
-  int ingest_bufs = 4;
-  int ingest_threads = 4;
-  std::vector<uint8_t*> h_stage;
-  std::vector<hipEvent_t> ev_stage;
-  size_t stage_bytes = 0;
-  hipStream_t copy_stream = nullptr;
+  // ingest (worker split -> HBM): the staging ring, its copy stream and the
+  // dgrep_set_ingest settings (ingest.h)
+  IngestRing ing;
   float last_ingest_ms = 0.f;
 
   // partition + intermediate writer (dgrep_encode_device / dgrep_map_partitions)
-  uint8_t* d_enc_scratch = nullptr;
-  uint64_t enc_scratch_cap = 0;
-  uint8_t* d_fname = nullptr;
-  uint64_t fname_cap = 0;
-  uint64_t* d_bounds = nullptr;
-  uint64_t bounds_cap = 0;
-  uint8_t* d_enc_out = nullptr;
-  uint64_t enc_out_cap = 0;
+  DevBuf<uint8_t> d_enc_scratch, d_fname;
+  DevBuf<uint64_t> d_bounds;
+  DevBuf<uint8_t> d_enc_out;
   float last_encode_ms = 0.f;
   uint32_t long_value = 0;  // dgrep_set_long_value: 0 = each writer's default (kLongValueDefault, kLongValueResidentDefault)
   dgrep_encode_stats enc_stats = {};  // dgrep_last_encode_stats (encode_ms is filled in by the getter)
 
   // many splits in one scan (dgrep_scan_batch*, kernels/batch.h)
-  uint64_t* d_bat_begin = nullptr;  // [k + 1]
-  uint64_t bat_begin_cap = 0;
-  unsigned long long* d_bat_lines = nullptr;  // [k]
-  uint64_t bat_lines_cap = 0;
-  unsigned long long* d_bat_sums = nullptr;   // [kBatchScanBlocks] + the separator flag
-  unsigned long long* h_bat_flag = nullptr;   // pinned: the flag's readback rides the scan's own host wait
-  std::vector<uint64_t> bat_begin;            // host copy of begin[] (read by an async upload)
-  std::vector<uint8_t> bat_stage;             // the direct ingest path's one staging buffer
-  uint32_t* d_res_split = nullptr;            // dgrep_scan_batch (host data) results, with d_res_*
-  uint64_t res_split_cap = 0;
-  uint64_t* d_res_sbegin = nullptr;
-  uint64_t res_sbegin_cap = 0;
-  hipEvent_t evb0 = nullptr, evb1 = nullptr, evb2 = nullptr, evb3 = nullptr;
+  DevBuf<uint64_t> d_bat_begin;             // [k + 1]
+  DevBuf<unsigned long long> d_bat_lines;   // [k]
+  DevBuf<unsigned long long> d_bat_sums;    // [kBatchScanBlocks] + the separator flag
+  PinnedBuf<unsigned long long> h_bat_flag;  // the flag's readback rides the scan's own host wait
+  std::vector<uint64_t> bat_begin;           // host copy of begin[] (read by an async upload)
+  DevBuf<uint32_t> d_res_split;              // dgrep_scan_batch (host data) results, with d_res_*
+  DevBuf<uint64_t> d_res_sbegin;
+  Event evb0, evb1, evb2, evb3;  // made by the first batch scan
   float last_newline_ms = 0.f, last_rebase_ms = 0.f;
   // partition writer over a batch (dgrep_map_partitions_batch / dgrep_encode_batch_device)
-  uint8_t* d_bat_names = nullptr;  // the filename table: offsets [k + 1], hash states [k], escaped names
-  uint64_t bat_names_cap = 0;
-  uint64_t* d_bat_cells = nullptr;  // [k * nreduce + 1]
-  uint64_t bat_cells_cap = 0;
+  DevBuf<uint8_t> d_bat_names;   // the filename table: offsets [k + 1], hash states [k], escaped names
+  DevBuf<uint64_t> d_bat_cells;  // [k * nreduce + 1]
 
   // reduce task (dgrep_reduce)
-  uint8_t* d_red_scratch = nullptr;
-  uint64_t red_scratch_cap = 0;
-  uint8_t* d_red_out = nullptr;
-  uint64_t red_out_cap = 0;
+  DevBuf<uint8_t> d_red_scratch, d_red_out;
   // every reduce task of a job in one pass (dgrep_reduce_batch* / dgrep_grep_job, kernels/reduce_batch.h)
-  uint64_t* d_rb_seg = nullptr;  // the segment table [nseg + 1] of the forms that take it from the host
-  uint64_t rb_seg_cap = 0;
-  uint64_t* d_rb_off = nullptr;  // part_off [nparts + 1], then lines_in [nparts]
-  uint64_t rb_off_cap = 0;
-  hipEvent_t evr0 = nullptr, evr1 = nullptr;
+  DevBuf<uint64_t> d_rb_seg;  // the segment table [nseg + 1] of the forms that take it from the host
+  DevBuf<uint64_t> d_rb_off;  // part_off [nparts + 1], then lines_in [nparts]
+  Event evr0, evr1;           // made by the first batch reduce
   float last_reduce_ms = 0.f;
   // the host pack buffer of the last closed job (dgrep_job_*): the next job takes it over, touched pages and all
   uint8_t* h_job_pack = nullptr;
@@ -271,15 +229,14 @@ int hip_fail(dgrep_ctx* c, hipError_t e, const char* what) {
     if (e_ != hipSuccess) return hip_fail(c, e_, #expr); \
   } while (0)
 
+// The discard-grow of a context, stream or job buffer (DevBuf::discard). The
+// early-out is inline: scan_resident makes about ten of these calls per scan.
 template <class T>
-int grow(dgrep_ctx* c, T** p, uint64_t* cap, uint64_t need) {
-  if (*cap >= need && *p) return DGREP_OK;
-  if (*p) HIPCHK(hipFree(*p));
-  *p = nullptr;
-  uint64_t n = std::max<uint64_t>(need, 1);
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  *cap = n;
-  return DGREP_OK;
+inline int grow(dgrep_ctx* c, DevBuf<T>& b, uint64_t need) {
+  if (b.holds(need)) return DGREP_OK;
+  const char* what = "";
+  const hipError_t e = b.discard(need, &what);
+  return e == hipSuccess ? DGREP_OK : hip_fail(c, e, what);
 }
 
 // Host wait per scan (scan_resident): block on the scan kernel's end event,
@@ -326,14 +283,11 @@ extern "C" int dgrep_open(int device, dgrep_ctx** out) {
   c->device = device;
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&c->num_cus, hipDeviceAttributeMultiprocessorCount, device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(&c->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&c->ev1);
-  if (e == hipSuccess) e = hipEventCreate(&c->ev2);
-  if (e == hipSuccess) e = hipEventCreate(&c->ev3);
-  if (e == hipSuccess) e = hipEventCreate(&c->ev4);
-  if (e == hipSuccess) e = hipEventCreate(&c->ev5);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->d_counters), kCounters * sizeof(unsigned long long));
+  if (e == hipSuccess) e = c->own_stream.create();
+  for (Event* ev : {&c->ev0, &c->ev1, &c->ev2, &c->ev3, &c->ev4, &c->ev5})
+    if (e == hipSuccess) e = ev->create();
+  const char* what = "";
+  if (e == hipSuccess) e = c->d_counters.discard(kCounters, &what);
   if (e != hipSuccess) {
     // keep the context so the caller can read the message
     c->err = std::string("dgrep_open: ") + hipGetErrorString(e);
@@ -350,32 +304,9 @@ extern "C" void dgrep_close(dgrep_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   free_pattern_device(&c->dev);
-  void* bufs[] = {c->d_spill, c->d_tails, c->d_chunk_nl, c->d_chunk_map,
-                  c->d_pend, c->d_seg, c->d_seg_off, c->d_segmap, c->d_seg_from, c->d_seg_state, c->d_tiles, c->d_out_off, c->d_line_base, c->d_staging, c->d_counters,
-                  c->d_overflow, c->d_data, c->d_res_line, c->d_res_start, c->d_res_len, c->d_enc_scratch,
-                  c->d_fname, c->d_bounds, c->d_enc_out, c->d_red_scratch, c->d_red_out, c->d_bat_begin,
-                  c->d_bat_lines, c->d_bat_sums, c->d_res_split, c->d_res_sbegin, c->d_bat_names, c->d_bat_cells,
-                  c->d_rb_seg, c->d_rb_off};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-  for (uint8_t* h : c->h_stage)
-    if (h) (void)hipHostFree(h);
-  for (hipEvent_t e : c->ev_stage)
-    if (e) (void)hipEventDestroy(e);
-  if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->ev2) (void)hipEventDestroy(c->ev2);
-  if (c->ev3) (void)hipEventDestroy(c->ev3);
-  if (c->ev4) (void)hipEventDestroy(c->ev4);
-  if (c->ev5) (void)hipEventDestroy(c->ev5);
-  for (hipEvent_t e : {c->evb0, c->evb1, c->evb2, c->evb3, c->evr0, c->evr1})
-    if (e) (void)hipEventDestroy(e);
-  if (c->h_bat_flag) (void)hipHostFree(c->h_bat_flag);
+  if (c->ing.copy_stream) (void)hipStreamSynchronize(c->ing.copy_stream);
   free(c->h_job_pack);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;  // its members release what they hold, the streams last
 }
 
 extern "C" const char* dgrep_last_error(dgrep_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -502,9 +433,9 @@ static int resolve_long_lines(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, u
     for (uint64_t b = P[i].resume; b < P[i].end; b += seg) segs.push_back(LongSeg{b, std::min(P[i].end, b + seg)});
     off[i + 1] = segs.size();
   }
-  if ((rc = grow(c, &c->d_seg, &c->seg_cap, std::max<uint64_t>(segs.size(), 1))) != DGREP_OK) return rc;
-  if ((rc = grow(c, &c->d_seg_off, &c->seg_off_cap, npend + 1)) != DGREP_OK) return rc;
-  if ((rc = grow(c, &c->d_segmap, &c->segmap_cap, std::max<uint64_t>(segs.size(), 1) * 256)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_seg, std::max<uint64_t>(segs.size(), 1))) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_seg_off, npend + 1)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_segmap, std::max<uint64_t>(segs.size(), 1) * 256)) != DGREP_OK) return rc;
   if (!segs.empty())
     HIPCHK(hipMemcpyAsync(c->d_seg, segs.data(), segs.size() * sizeof(LongSeg), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->d_seg_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
@@ -560,11 +491,11 @@ static int resolve_long_filter(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, 
     off[i + 1] = segs.size();
   }
   const uint64_t ns = std::max<uint64_t>(segs.size(), 1);
-  if ((rc = grow(c, &c->d_seg, &c->seg_cap, ns)) != DGREP_OK) return rc;
-  if ((rc = grow(c, &c->d_seg_from, &c->seg_from_cap, ns)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_seg, ns)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_seg_from, ns)) != DGREP_OK) return rc;
   const uint64_t ng = long_guesses();
-  if ((rc = grow(c, &c->d_seg_state, &c->seg_state_cap, 2 * ng * ns)) != DGREP_OK) return rc;
-  if ((rc = grow(c, &c->d_seg_off, &c->seg_off_cap, npend + 1)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_seg_state, 2 * ng * ns)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_seg_off, npend + 1)) != DGREP_OK) return rc;
   if (!segs.empty()) {
     HIPCHK(hipMemcpyAsync(c->d_seg, segs.data(), segs.size() * sizeof(LongSeg), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_seg_from, from.data(), from.size() * 8, hipMemcpyHostToDevice, c->stream));
@@ -610,6 +541,26 @@ static int resolve_long_filter(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, 
   return DGREP_OK;
 }
 
+// long_lines_sheng's arguments: the Sheng stepper's parked lines, resolved
+// through the chunk maps
+static LongArgs sheng_long_args(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64_t chunk, uint64_t nchunks,
+                                uint64_t npend) {
+  LongArgs la;
+  memset(&la, 0, sizeof la);
+  la.n = n;
+  la.chunk = chunk;
+  la.nchunks = nchunks;
+  la.pend = c->d_pend;
+  la.npend = npend;
+  la.chunk_map = c->d_chunk_map;
+  la.sheng_m = c->pat.start_m;
+  la.nl_lo = c->pat.sheng_nl_lo;
+  la.nl_hi = c->pat.sheng_nl_hi;
+  la.sheng_v = reinterpret_cast<const uint2*>(c->dev.table);
+  la.data = d_data;
+  return la;
+}
+
 // Core of every scan: the split is resident at d_data (n bytes). Results go to
 // device arrays of `capacity` lines; *count receives the number of matches.
 static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64_t* d_line, uint64_t* d_start,
@@ -645,27 +596,26 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
                                         DGREP_SPILL_RECORDS, &chunk, &wpb, &slots, &threads, &spills);
   const uint64_t ntiles = (n + tile - 1) / tile;
   int rc;
-  if ((rc = grow(c, &c->d_tiles, &c->tiles_cap, ntiles)) != DGREP_OK) return rc;
-  if ((rc = grow(c, &c->d_out_off, &c->off_cap, ntiles + 1)) != DGREP_OK) return rc;
-  if ((rc = grow(c, &c->d_line_base, &c->lb_cap, ntiles + 1)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_tiles, ntiles)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_out_off, ntiles + 1)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_line_base, ntiles + 1)) != DGREP_OK) return rc;
   // kStepFilter stages its candidates too: the staging buffer holds at least
   // the previous scan's staged lines, and grows (one re-scan) if they overflow
   const bool filt = c->pat.step_kind == kStepFilter && c->pat.cand_end != UINT32_MAX;
-  if ((rc = grow(c, &c->d_staging, &c->staging_cap, filt ? std::max(capacity, c->staged_hint) : capacity)) != DGREP_OK)
+  if ((rc = grow(c, c->d_staging, filt ? std::max(capacity, c->staged_hint) : capacity)) != DGREP_OK)
     return rc;
 
-  if (!c->d_overflow && (rc = grow(c, &c->d_overflow, &c->overflow_cap, 1u << 16)) != DGREP_OK) return rc;
+  if (!c->d_overflow && (rc = grow(c, c->d_overflow, 1u << 16)) != DGREP_OK) return rc;
   const int grid = int(std::min<uint64_t>(ntiles, resident));
   // chunks per lane (the two-stream steppers step two in lockstep)
   const uint32_t streams = tile / (uint64_t(kTileLanes) * chunk);
   const bool use_spill = spills && DGREP_SPILL_RECORDS > 0;
-  if (use_spill && (rc = grow(c, &c->d_spill, &c->spill_cap,
-                              uint64_t(grid) * threads * streams * DGREP_SPILL_RECORDS)) != DGREP_OK)
+  if (use_spill && (rc = grow(c, c->d_spill, uint64_t(grid) * threads * streams * DGREP_SPILL_RECORDS)) != DGREP_OK)
     return rc;
   // long lines: the lanes' tail entries, '\n' per chunk and the pending list
   // (parking needs the blob's table: <= 256-state DFAs on the Sheng / pair /
   // table steppers)
-  if ((rc = grow(c, &c->d_tails, &c->tails_cap, uint64_t(grid) * threads * streams)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_tails, uint64_t(grid) * threads * streams)) != DGREP_OK) return rc;
   // the filter parks too when the whole DFA is at hand (not a partial blob, whose
   // candidates an NFA program decides: its lanes read a long line on)
   const bool park_filter = DGREP_PARK && c->pat.step_kind == kStepFilter && c->dev.full != nullptr;
@@ -675,11 +625,11 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
   const bool park_maps = park && c->pat.step_kind == kStepSheng8 && DGREP_SHENG_MAPS;
   if (park) {
     if (park_maps) {
-      if ((rc = grow(c, &c->d_chunk_map, &c->chunk_map_cap, nchunks)) != DGREP_OK) return rc;
-    } else if ((rc = grow(c, &c->d_chunk_nl, &c->chunk_nl_cap, nchunks)) != DGREP_OK) {
+      if ((rc = grow(c, c->d_chunk_map, nchunks)) != DGREP_OK) return rc;
+    } else if ((rc = grow(c, c->d_chunk_nl, nchunks)) != DGREP_OK) {
       return rc;
     }
-    if (!c->d_pend && (rc = grow(c, &c->d_pend, &c->pend_cap, 1024)) != DGREP_OK) return rc;
+    if (!c->d_pend && (rc = grow(c, c->d_pend, 1024)) != DGREP_OK) return rc;
   }
 
   ScanArgs a;
@@ -731,11 +681,11 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
   bool settled = false;
   for (int attempt = 0; attempt < 4 && !settled; ++attempt) {
     a.staging = c->d_staging;
-    a.capacity = c->staging_cap;
+    a.capacity = c->d_staging.cap;
     a.overflow = c->d_overflow;
-    a.overflow_cap = c->overflow_cap;
+    a.overflow_cap = c->d_overflow.cap;
     a.pend = park ? c->d_pend : nullptr;
-    a.pend_cap = park ? c->pend_cap : 0;
+    a.pend_cap = park ? c->d_pend.cap : 0;
     HIPCHK(hipMemsetAsync(c->d_counters, 0, kCounters * sizeof(unsigned long long), c->stream));
     HIPCHK(hipEventRecord(c->ev0, c->stream));
     HIPCHK(scan_dfa(launch_kind(c->pat), a, grid, c->stream));
@@ -744,7 +694,7 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
     // lane overflowed or a line was parked: entries [count, capacity) are never
     // written, and a parked line that does not match would be one)
     if (speculate)
-      HIPCHK(order_lines(c->d_tiles, c->d_staging, ntiles, c->d_out_off, c->d_line_base, c->staging_cap, capacity,
+      HIPCHK(order_lines(c->d_tiles, c->d_staging, ntiles, c->d_out_off, c->d_line_base, c->d_staging.cap, capacity,
                          d_line, d_start, d_len, c->d_counters, c->stream));
     HIPCHK(hipMemcpyAsync(ctr, c->d_counters, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
     if (DGREP_SYNC_SPIN_US > 0) {
@@ -765,23 +715,23 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
     HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     S.scan_ms += ms;  // a re-run scan is counted: it is part of this call's device time
     ++S.scan_attempts;
-    if (ctr[1] > c->overflow_cap) {
+    if (ctr[1] > c->d_overflow.cap) {
       // more overflowing lanes than recorded: grow the list and scan again
-      if ((rc = grow(c, &c->d_overflow, &c->overflow_cap, ctr[1])) != DGREP_OK) return rc;
-    } else if (park && ctr[2] > c->pend_cap) {
+      if ((rc = grow(c, c->d_overflow, ctr[1])) != DGREP_OK) return rc;
+    } else if (park && ctr[2] > c->d_pend.cap) {
       // more parked long lines than the pending list holds
-      if ((rc = grow(c, &c->d_pend, &c->pend_cap, ctr[2])) != DGREP_OK) return rc;
-    } else if (filt && ctr[0] > c->staging_cap) {
+      if ((rc = grow(c, c->d_pend, ctr[2])) != DGREP_OK) return rc;
+    } else if (filt && ctr[0] > c->d_staging.cap) {
       // candidates included, more staged lines than the staging buffer holds
-      if ((rc = grow(c, &c->d_staging, &c->staging_cap, ctr[0] + ctr[0] / 8)) != DGREP_OK) return rc;
-    } else if (park && ctr[2] && ctr[0] > c->staging_cap && capacity != 0 && ctr[0] - ctr[2] <= capacity) {
+      if ((rc = grow(c, c->d_staging, ctr[0] + ctr[0] / 8)) != DGREP_OK) return rc;
+    } else if (park && ctr[2] && ctr[0] > c->d_staging.cap && capacity != 0 && ctr[0] - ctr[2] <= capacity) {
       // every parked line is staged as one record whether it matches or not: the
       // staged lines outgrew the staging buffer (sized by `capacity`), but the
       // matching ones may still fit the caller's arrays once the parked lines
       // that do not match are dropped -- and only complete staging can be
       // resolved and ordered. (Ordering the truncated staging here returned a
       // count <= capacity with wrong records.)
-      if ((rc = grow(c, &c->d_staging, &c->staging_cap, ctr[0])) != DGREP_OK) return rc;
+      if ((rc = grow(c, c->d_staging, ctr[0])) != DGREP_OK) return rc;
     } else {
       settled = true;
     }
@@ -821,7 +771,7 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
     v.tiles = c->d_tiles;
     v.ntiles = ntiles;
     v.staging = c->d_staging;
-    v.staging_cap = c->staging_cap;
+    v.staging_cap = c->d_staging.cap;
     v.removed = c->d_counters + 3;  // zeroed before the scan
     v.nfa = c->dev.nfa;
     v.nfa_words = c->pat.nfa_words;
@@ -834,20 +784,7 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
     v.num_cus = uint32_t(c->num_cus);
     HIPCHK(hipEventRecord(c->ev4, c->stream));
     if (npend && park_maps) {
-      LongArgs la;
-      memset(&la, 0, sizeof la);
-      la.n = n;
-      la.chunk = chunk;
-      la.nchunks = nchunks;
-      la.pend = c->d_pend;
-      la.npend = npend;
-      la.chunk_map = c->d_chunk_map;
-      la.sheng_m = c->pat.start_m;
-      la.nl_lo = c->pat.sheng_nl_lo;
-      la.nl_hi = c->pat.sheng_nl_hi;
-      la.sheng_v = reinterpret_cast<const uint2*>(c->dev.table);
-      la.data = d_data;
-      HIPCHK(long_lines_sheng(la, c->stream));
+      HIPCHK(long_lines_sheng(sheng_long_args(c, d_data, n, chunk, nchunks, npend), c->stream));
     } else if (npend && park_filter) {
       if ((rc = resolve_long_filter(c, d_data, n, chunk, nchunks, npend)) != DGREP_OK) return rc;
     } else if (npend && (rc = resolve_long_lines(c, d_data, n, chunk, nchunks, npend)) != DGREP_OK) {
@@ -861,7 +798,7 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
     // staged line fits the output, order them before the one host wait (the
     // kept lines are fewer still; a separate wait cost C4 ~30 us a scan)
     if (capacity != 0 && staged <= capacity) {
-      HIPCHK(order_lines(c->d_tiles, c->d_staging, ntiles, c->d_out_off, c->d_line_base, c->staging_cap, capacity,
+      HIPCHK(order_lines(c->d_tiles, c->d_staging, ntiles, c->d_out_off, c->d_line_base, c->d_staging.cap, capacity,
                          d_line, d_start, d_len, nullptr, c->stream));
       ordered = true;
     }
@@ -878,20 +815,7 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
     // match. (Overflow lanes were counted in full by the scan: no pass needed.)
     HIPCHK(hipEventRecord(c->ev4, c->stream));
     if (park_maps) {
-      LongArgs la;
-      memset(&la, 0, sizeof la);
-      la.n = n;
-      la.chunk = chunk;
-      la.nchunks = nchunks;
-      la.pend = c->d_pend;
-      la.npend = npend;
-      la.chunk_map = c->d_chunk_map;
-      la.sheng_m = c->pat.start_m;
-      la.nl_lo = c->pat.sheng_nl_lo;
-      la.nl_hi = c->pat.sheng_nl_hi;
-      la.sheng_v = reinterpret_cast<const uint2*>(c->dev.table);
-      la.data = d_data;
-      HIPCHK(long_lines_sheng(la, c->stream));
+      HIPCHK(long_lines_sheng(sheng_long_args(c, d_data, n, chunk, nchunks, npend), c->stream));
     } else if ((rc = park_filter ? resolve_long_filter(c, d_data, n, chunk, nchunks, npend)
                                  : resolve_long_lines(c, d_data, n, chunk, nchunks, npend)) != DGREP_OK) {
       return rc;
@@ -914,7 +838,7 @@ static int scan_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64
   const bool spec_stands = speculate && !ctr[1] && !ctr[2];
   const bool order = total != 0 && total <= capacity && !spec_stands && !ordered;
   if (order)
-    HIPCHK(order_lines(c->d_tiles, c->d_staging, ntiles, c->d_out_off, c->d_line_base, c->staging_cap, capacity,
+    HIPCHK(order_lines(c->d_tiles, c->d_staging, ntiles, c->d_out_off, c->d_line_base, c->d_staging.cap, capacity,
                        d_line, d_start, d_len, nullptr, c->stream));
   if (over || order) HIPCHK(hipStreamSynchronize(c->stream));
   if (over) {
@@ -937,69 +861,35 @@ extern "C" int dgrep_scan_device(dgrep_ctx* c, const void* d_data, size_t n, uin
   return rc;
 }
 
-// Worker-side ingest of one split (the bytes map_reduce/worker.go:72-76
-// read with os.ReadFile and hand to Map): host -> pinned staging -> HBM.
-// Piece k is memcpy'd by the CPU threads into staging buffer k % B once the
-// DMA that last read that buffer has finished, then DMA'd on the copy stream;
-// so the CPU copy of piece k+1 overlaps the DMA of piece k. The scan stream
-// waits on the last DMA. A split of at most one piece below 4 MiB, or chunk
-// 0, takes one pageable hipMemcpyAsync instead.
-static int ingest(dgrep_ctx* c, const uint8_t* data, size_t n) {
+// a failed call of ingest.h, as HIPCHK reports one
+#define INGCHK(expr)                                             \
+  do {                                                           \
+    hipError_t e_ = (expr);                                      \
+    if (e_ != hipSuccess) return hip_fail(c, e_, c->ing.what);   \
+  } while (0)
+
+// Worker-side ingest (the bytes map_reduce/worker.go:72-76 read with
+// os.ReadFile and hand to Map) with the resident completion contract: P (k
+// buffers, `total` bytes, ingest.h) -> c->d_data. On the ring path the first
+// DMA waits for earlier work on the context stream (the previous scan may still
+// read d_data), the context stream is ordered behind the last DMA and the copy
+// stream is drained: the caller's bytes are free on return. The direct path is
+// one copy on the context stream.
+static int ingest_resident(dgrep_ctx* c, const uint8_t* const* data, const size_t* n, size_t k, size_t total,
+                           bool sep = true) {
   const auto t0 = std::chrono::steady_clock::now();
-  if (c->ingest_chunk == 0 || n < (size_t(4) << 20)) {
-    HIPCHK(hipMemcpyAsync(c->d_data, data, n, hipMemcpyHostToDevice, c->stream));
+  IngestRing* r = &c->ing;
+  if (ingest_direct(*r, total)) {
+    INGCHK(ingest_direct_copy(r, data, n, k, sep, c->d_data, total, c->stream));
     c->last_ingest_ms = 0.f;
     return DGREP_OK;
   }
-  const size_t S = c->ingest_chunk;
-  const int B = std::max(2, c->ingest_bufs);
-  if (c->stage_bytes != S || int(c->h_stage.size()) != B) {
-    if (c->copy_stream) HIPCHK(hipStreamSynchronize(c->copy_stream));
-    for (uint8_t* h : c->h_stage)
-      if (h) HIPCHK(hipHostFree(h));
-    for (hipEvent_t e : c->ev_stage)
-      if (e) HIPCHK(hipEventDestroy(e));
-    c->h_stage.assign(B, nullptr);
-    c->ev_stage.assign(B, nullptr);
-    c->stage_bytes = 0;
-    for (int b = 0; b < B; ++b) {
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage[b]), S, hipHostMallocDefault));
-      HIPCHK(hipEventCreateWithFlags(&c->ev_stage[b], hipEventDisableTiming));
-    }
-    c->stage_bytes = S;
-  }
-  if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  // the previous scan may still read d_data: the first DMA waits for it
+  INGCHK(ingest_ring(r));
   HIPCHK(hipEventRecord(c->ev1, c->stream));
-  HIPCHK(hipStreamWaitEvent(c->copy_stream, c->ev1, 0));
-  const int T = std::max(1, c->ingest_threads);
-  std::vector<bool> used(B, false);
-  const size_t pieces = (n + S - 1) / S;
-  for (size_t k = 0; k < pieces; ++k) {
-    const int b = int(k % size_t(B));
-    const size_t off = k * S, len = std::min(S, n - off);
-    if (used[b]) HIPCHK(hipEventSynchronize(c->ev_stage[b]));  // buffer b's last DMA is done
-    uint8_t* dst = c->h_stage[b];
-    const uint8_t* src = data + off;
-    if (T == 1 || len < (size_t(1) << 20)) {
-      memcpy(dst, src, len);
-    } else {
-      std::vector<std::thread> th;
-      const size_t part = ((len + T - 1) / T + 4095) & ~size_t(4095);
-      for (int t = 0; t < T; ++t) {
-        const size_t a = size_t(t) * part;
-        if (a >= len) break;
-        const size_t m = std::min(part, len - a);
-        th.emplace_back([=] { memcpy(dst + a, src + a, m); });
-      }
-      for (auto& x : th) x.join();
-    }
-    HIPCHK(hipMemcpyAsync(c->d_data + off, dst, len, hipMemcpyHostToDevice, c->copy_stream));
-    HIPCHK(hipEventRecord(c->ev_stage[b], c->copy_stream));
-    used[b] = true;
-  }
-  HIPCHK(hipStreamWaitEvent(c->stream, c->ev_stage[int((pieces - 1) % size_t(B))], 0));
-  HIPCHK(hipStreamSynchronize(c->copy_stream));
+  HIPCHK(hipStreamWaitEvent(r->copy_stream, c->ev1, 0));
+  INGCHK(ingest_pieces(r, data, n, k, sep, c->d_data, total));
+  HIPCHK(hipStreamWaitEvent(c->stream, r->ev_stage[r->last], 0));
+  HIPCHK(hipStreamSynchronize(r->copy_stream));
   c->last_ingest_ms =
       std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return DGREP_OK;
@@ -1007,9 +897,9 @@ static int ingest(dgrep_ctx* c, const uint8_t* data, size_t n) {
 
 extern "C" int dgrep_set_ingest(dgrep_ctx* c, size_t chunk_bytes, int nbufs, int threads) {
   if (!c || nbufs < 0 || threads < 0 || nbufs > 64 || threads > 256) return DGREP_E_INVALID;
-  c->ingest_chunk = chunk_bytes;
-  if (nbufs) c->ingest_bufs = nbufs;
-  if (threads) c->ingest_threads = threads;
+  c->ing.chunk = chunk_bytes;
+  if (nbufs) c->ing.bufs = nbufs;
+  if (threads) c->ing.threads = threads;
   return DGREP_OK;
 }
 
@@ -1021,16 +911,34 @@ extern "C" int dgrep_last_ingest_ms(dgrep_ctx* c, float* ms) {
 
 // The context's result arrays, at least `want` lines each.
 static int grow_results(dgrep_ctx* c, uint64_t want) {
-  if (want <= c->res_cap) return DGREP_OK;
   int rc;
-  uint64_t c1 = 0, c2 = 0, c3 = 0;
-  if (c->d_res_line) { HIPCHK(hipFree(c->d_res_line)); c->d_res_line = nullptr; }
-  if (c->d_res_start) { HIPCHK(hipFree(c->d_res_start)); c->d_res_start = nullptr; }
-  if (c->d_res_len) { HIPCHK(hipFree(c->d_res_len)); c->d_res_len = nullptr; }
-  if ((rc = grow(c, &c->d_res_line, &c1, want)) != DGREP_OK) return rc;
-  if ((rc = grow(c, &c->d_res_start, &c2, want)) != DGREP_OK) return rc;
-  if ((rc = grow(c, &c->d_res_len, &c3, want)) != DGREP_OK) return rc;
-  c->res_cap = want;
+  if ((rc = grow(c, c->d_res_line, want)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_res_start, want)) != DGREP_OK) return rc;
+  return grow(c, c->d_res_len, want);
+}
+
+// One array of a result fetch: *host = malloc(lead + bytes) (nothing when that
+// is 0), and `bytes` from dev copied in behind the lead.
+struct Fetch {
+  void* host;  // T**
+  const void* dev;
+  size_t bytes, lead;
+};
+
+// Device results to malloc'd host arrays: every allocation first, and with one
+// missing DGREP_E_NOMEM (the caller frees its struct); then the copies on the
+// context stream and one synchronise.
+static int fetch_results(dgrep_ctx* c, std::initializer_list<Fetch> arrays) {
+  bool ok = true, copies = false;
+  for (const Fetch& f : arrays)
+    if (f.lead + f.bytes) ok = (*static_cast<void**>(f.host) = malloc(f.lead + f.bytes)) != nullptr && ok;
+  if (!ok) return DGREP_E_NOMEM;
+  for (const Fetch& f : arrays) {
+    if (!f.bytes) continue;
+    HIPCHK(hipMemcpyAsync(*static_cast<uint8_t**>(f.host) + f.lead, f.dev, f.bytes, hipMemcpyDeviceToHost, c->stream));
+    copies = true;
+  }
+  if (copies) HIPCHK(hipStreamSynchronize(c->stream));
   return DGREP_OK;
 }
 
@@ -1038,18 +946,16 @@ static int grow_results(dgrep_ctx* c, uint64_t want) {
 static int scan_host(dgrep_ctx* c, const uint8_t* data, size_t n, uint64_t* count) {
   int rc;
   if (n) {
-    uint64_t cap = c->data_cap;
-    if ((rc = grow(c, &c->d_data, &cap, (n + 63) & ~uint64_t(63))) != DGREP_OK) return rc;
-    c->data_cap = cap;
-    if ((rc = ingest(c, data, n)) != DGREP_OK) return rc;
+    if ((rc = grow(c, c->d_data, (n + 63) & ~uint64_t(63))) != DGREP_OK) return rc;
+    if ((rc = ingest_resident(c, &data, &n, 1, n)) != DGREP_OK) return rc;
   }
-  uint64_t want = std::max<uint64_t>(c->res_cap, std::max<uint64_t>(1024, n / 512));
+  uint64_t want = std::max<uint64_t>(c->d_res_line.cap, std::max<uint64_t>(1024, n / 512));
   for (int attempt = 0; attempt < 2; ++attempt) {
     if ((rc = grow_results(c, want)) != DGREP_OK) return rc;
-    if ((rc = scan_resident(c, c->d_data, n, c->d_res_line, c->d_res_start, c->d_res_len, c->res_cap, count)) !=
+    if ((rc = scan_resident(c, c->d_data, n, c->d_res_line, c->d_res_start, c->d_res_len, c->d_res_line.cap, count)) !=
         DGREP_OK)
       return rc;
-    if (*count <= c->res_cap) break;
+    if (*count <= c->d_res_line.cap) break;
     want = *count;
   }
   return DGREP_OK;
@@ -1065,18 +971,11 @@ extern "C" int dgrep_scan(dgrep_ctx* c, const uint8_t* data, size_t n, dgrep_res
   if ((rc = scan_host(c, data, n, &count)) != DGREP_OK) return rc;
   out->count = count;
   if (count == 0) return DGREP_OK;
-  out->line_no = static_cast<uint64_t*>(malloc(count * 8));
-  out->start = static_cast<uint64_t*>(malloc(count * 8));
-  out->len = static_cast<uint64_t*>(malloc(count * 8));
-  if (!out->line_no || !out->start || !out->len) {
-    dgrep_result_free(out);
-    return DGREP_E_NOMEM;
-  }
-  HIPCHK(hipMemcpyAsync(out->line_no, c->d_res_line, count * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(out->start, c->d_res_start, count * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(out->len, c->d_res_len, count * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return DGREP_OK;
+  const size_t b = count * 8;
+  rc = fetch_results(c, {{&out->line_no, c->d_res_line, b, 0}, {&out->start, c->d_res_start, b, 0},
+                         {&out->len, c->d_res_len, b, 0}});
+  if (rc == DGREP_E_NOMEM) dgrep_result_free(out);
+  return rc;
 }
 
 // ---- many splits in one scan (kernels/batch.h) ------------------------------
@@ -1088,13 +987,11 @@ extern "C" int dgrep_scan(dgrep_ctx* c, const uint8_t* data, size_t n, dgrep_res
 // The batch scratch for k splits, and begin[] (c->bat_begin, k + 1 entries).
 static int batch_setup(dgrep_ctx* c, const uint64_t* len, uint64_t k) {
   int rc;
-  if ((rc = grow(c, &c->d_bat_begin, &c->bat_begin_cap, k + 1)) != DGREP_OK) return rc;
-  if ((rc = grow(c, &c->d_bat_lines, &c->bat_lines_cap, k)) != DGREP_OK) return rc;
-  if (!c->d_bat_sums)
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_bat_sums), (kBatchScanBlocks + 1) * sizeof(unsigned long long)));
-  if (!c->h_bat_flag) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_bat_flag), 8, hipHostMallocDefault));
-  for (hipEvent_t* e : {&c->evb0, &c->evb1, &c->evb2, &c->evb3})
-    if (!*e) HIPCHK(hipEventCreate(e));
+  if ((rc = grow(c, c->d_bat_begin, k + 1)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_bat_lines, k)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_bat_sums, kBatchScanBlocks + 1)) != DGREP_OK) return rc;
+  HIPCHK(c->h_bat_flag.alloc(1));
+  for (Event* e : {&c->evb0, &c->evb1, &c->evb2, &c->evb3}) HIPCHK(e->create());
   c->bat_begin.resize(k + 1);
   uint64_t b = 0;
   for (uint64_t i = 0; i < k; ++i) {
@@ -1195,93 +1092,6 @@ extern "C" int dgrep_scan_batch_device(dgrep_ctx* c, const void* d_packed, size_
   return rc;
 }
 
-// The pinned staging ring of the ingest, as ingest() sets it up.
-static int ingest_ring(dgrep_ctx* c, size_t S, int B) {
-  if (c->stage_bytes != S || int(c->h_stage.size()) != B) {
-    if (c->copy_stream) HIPCHK(hipStreamSynchronize(c->copy_stream));
-    for (uint8_t* h : c->h_stage)
-      if (h) HIPCHK(hipHostFree(h));
-    for (hipEvent_t e : c->ev_stage)
-      if (e) HIPCHK(hipEventDestroy(e));
-    c->h_stage.assign(B, nullptr);
-    c->ev_stage.assign(B, nullptr);
-    c->stage_bytes = 0;
-    for (int b = 0; b < B; ++b) {
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage[b]), S, hipHostMallocDefault));
-      HIPCHK(hipEventCreateWithFlags(&c->ev_stage[b], hipEventDisableTiming));
-    }
-    c->stage_bytes = S;
-  }
-  if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  return DGREP_OK;
-}
-
-// ingest() for a batch: the packed buffer is never built on the host. Each
-// pinned staging piece is filled from the runs of source splits and separator
-// bytes that fall into it (pack_pieces.h), then DMA'd as in ingest(): the same
-// ring, copy stream and settings. Below 4 MiB, or with chunk 0, the whole of P
-// is assembled in one host staging buffer and copied with one hipMemcpyAsync.
-// `sep` = false lays the inputs back to back with no separator byte (the batch
-// reduce's inputs; `total` is then their plain sum).
-static int ingest_packed(dgrep_ctx* c, const uint8_t* const* data, const size_t* n, size_t k, size_t total,
-                         bool sep = true) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const int T = std::max(1, c->ingest_threads);
-  PackCursor cur;
-  std::vector<PackSeg> segs;
-  auto fill = [&](uint8_t* dst, size_t len) {
-    pack_piece_segments(n, k, &cur, len, &segs, sep);
-    for (const PackSeg& s : segs) {
-      if (T == 1 || s.split == kPackSeparator || s.len < (size_t(1) << 20)) {
-        pack_copy_segment(data, s, dst);
-        continue;
-      }
-      std::vector<std::thread> th;
-      const size_t part = ((s.len + T - 1) / T + 4095) & ~size_t(4095);
-      uint8_t* d = dst + s.dst_off;
-      const uint8_t* src = data[s.split] + s.src_off;
-      const size_t len_s = s.len;
-      for (int t = 0; t < T; ++t) {
-        const size_t a = size_t(t) * part;
-        if (a >= len_s) break;
-        const size_t m = std::min(part, len_s - a);
-        th.emplace_back([=] { memcpy(d + a, src + a, m); });
-      }
-      for (auto& x : th) x.join();
-    }
-  };
-  if (c->ingest_chunk == 0 || total < (size_t(4) << 20)) {
-    c->bat_stage.resize(total);
-    fill(c->bat_stage.data(), total);
-    HIPCHK(hipMemcpyAsync(c->d_data, c->bat_stage.data(), total, hipMemcpyHostToDevice, c->stream));
-    c->last_ingest_ms = 0.f;
-    return DGREP_OK;
-  }
-  const size_t S = c->ingest_chunk;
-  const int B = std::max(2, c->ingest_bufs);
-  int rc;
-  if ((rc = ingest_ring(c, S, B)) != DGREP_OK) return rc;
-  // the previous scan may still read d_data: the first DMA waits for it
-  HIPCHK(hipEventRecord(c->ev1, c->stream));
-  HIPCHK(hipStreamWaitEvent(c->copy_stream, c->ev1, 0));
-  std::vector<bool> used(B, false);
-  const size_t pieces = (total + S - 1) / S;
-  for (size_t p = 0; p < pieces; ++p) {
-    const int b = int(p % size_t(B));
-    const size_t off = p * S, len = std::min(S, total - off);
-    if (used[b]) HIPCHK(hipEventSynchronize(c->ev_stage[b]));  // buffer b's last DMA is done
-    fill(c->h_stage[b], len);
-    HIPCHK(hipMemcpyAsync(c->d_data + off, c->h_stage[b], len, hipMemcpyHostToDevice, c->copy_stream));
-    HIPCHK(hipEventRecord(c->ev_stage[b], c->copy_stream));
-    used[b] = true;
-  }
-  HIPCHK(hipStreamWaitEvent(c->stream, c->ev_stage[int((pieces - 1) % size_t(B))], 0));
-  HIPCHK(hipStreamSynchronize(c->copy_stream));
-  c->last_ingest_ms =
-      std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return DGREP_OK;
-}
-
 // Host splits -> packed ingest -> batch scan into the context's result arrays
 // (d_res_line / start / len / split, and d_res_sbegin when `ranges`), grown and
 // re-scanned once if the first guess at the record count was too small.
@@ -1291,21 +1101,19 @@ static int batch_scan_host(dgrep_ctx* c, const uint8_t* const* data, const size_
   static_assert(sizeof(size_t) == sizeof(uint64_t), "split lengths are passed on as u64");
   if ((rc = batch_setup(c, reinterpret_cast<const uint64_t*>(n), nsplits)) != DGREP_OK) return rc;
   if (total) {
-    uint64_t cap = c->data_cap;
-    if ((rc = grow(c, &c->d_data, &cap, (uint64_t(total) + 63) & ~uint64_t(63))) != DGREP_OK) return rc;
-    c->data_cap = cap;
-    if ((rc = ingest_packed(c, data, n, nsplits, total)) != DGREP_OK) return rc;
+    if ((rc = grow(c, c->d_data, (uint64_t(total) + 63) & ~uint64_t(63))) != DGREP_OK) return rc;
+    if ((rc = ingest_resident(c, data, n, nsplits, total)) != DGREP_OK) return rc;
   }
-  if (ranges && (rc = grow(c, &c->d_res_sbegin, &c->res_sbegin_cap, uint64_t(nsplits) + 1)) != DGREP_OK) return rc;
-  uint64_t want = std::max<uint64_t>(c->res_cap, std::max<uint64_t>(1024, total / 512));
+  if (ranges && (rc = grow(c, c->d_res_sbegin, uint64_t(nsplits) + 1)) != DGREP_OK) return rc;
+  uint64_t want = std::max<uint64_t>(c->d_res_line.cap, std::max<uint64_t>(1024, total / 512));
   uint64_t count = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
     if ((rc = grow_results(c, want)) != DGREP_OK) return rc;
-    if ((rc = grow(c, &c->d_res_split, &c->res_split_cap, c->res_cap)) != DGREP_OK) return rc;
+    if ((rc = grow(c, c->d_res_split, c->d_res_line.cap)) != DGREP_OK) return rc;
     if ((rc = batch_resident(c, c->d_data, total, nsplits, c->d_res_line, c->d_res_start, c->d_res_len, c->d_res_split,
-                             ranges ? c->d_res_sbegin : nullptr, c->res_cap, &count, attempt == 0)) != DGREP_OK)
+                             ranges ? c->d_res_sbegin : nullptr, c->d_res_line.cap, &count, attempt == 0)) != DGREP_OK)
       return rc;
-    if (count <= c->res_cap) break;
+    if (count <= c->d_res_line.cap) break;
     want = count;
   }
   *count_out = count;
@@ -1330,26 +1138,14 @@ extern "C" int dgrep_scan_batch(dgrep_ctx* c, const uint8_t* const* data, const 
   if ((rc = batch_scan_host(c, data, n, nsplits, total, true, &count)) != DGREP_OK) return rc;
   out->count = count;
   out->nsplits = nsplits;
-  out->split_begin = static_cast<uint64_t*>(malloc((nsplits + 1) * 8));
-  if (count) {
-    out->line_no = static_cast<uint64_t*>(malloc(count * 8));
-    out->start = static_cast<uint64_t*>(malloc(count * 8));
-    out->len = static_cast<uint64_t*>(malloc(count * 8));
-    out->split = static_cast<uint32_t*>(malloc(count * 4));
-  }
-  if (!out->split_begin || (count && (!out->line_no || !out->start || !out->len || !out->split))) {
-    dgrep_batch_result_free(out);
-    return DGREP_E_NOMEM;
-  }
-  HIPCHK(hipMemcpyAsync(out->split_begin, c->d_res_sbegin, (nsplits + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  if (count) {
-    HIPCHK(hipMemcpyAsync(out->line_no, c->d_res_line, count * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(out->start, c->d_res_start, count * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(out->len, c->d_res_len, count * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(out->split, c->d_res_split, count * 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return DGREP_OK;
+  const size_t b = count * 8;
+  rc = fetch_results(c, {{&out->split_begin, c->d_res_sbegin, (nsplits + 1) * 8, 0},
+                         {&out->line_no, c->d_res_line, b, 0},
+                         {&out->start, c->d_res_start, b, 0},
+                         {&out->len, c->d_res_len, b, 0},
+                         {&out->split, c->d_res_split, count * 4, 0}});
+  if (rc == DGREP_E_NOMEM) dgrep_batch_result_free(out);
+  return rc;
 }
 
 extern "C" void dgrep_batch_result_free(dgrep_batch_result* r) {
@@ -1390,27 +1186,22 @@ struct dgrep_stream {
   int status = DGREP_OK;   // a HIP error or out-of-memory mid-stream: every later call returns it
   bool finished = false;
   // the two window buffers; buf[cur][0 : fill) is the carried tail
-  uint8_t* buf[2] = {nullptr, nullptr};
-  uint64_t cap[2] = {0, 0};
+  DevBuf<uint8_t> buf[2];
   int cur = 0;
   uint64_t fill = 0;
   uint64_t byte_base = 0, line_base = 0;
   // device: the cut pass's partials [3 kCutBlocks], its result [3], the gather's total [1]; pinned: the last four
-  unsigned long long* d_cut = nullptr;
-  unsigned long long* h_cut = nullptr;
-  hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;   // the cut pass
-  hipEvent_t ev_free[2] = {nullptr, nullptr};    // buffer b's last reader on the context stream
-  hipEvent_t ev_in = nullptr;                    // the last copy into buf[cur] on the copy stream
+  DevBuf<unsigned long long> d_cut;
+  PinnedBuf<unsigned long long> h_cut;
+  Event ev_c0, ev_c1;  // the cut pass
+  Event ev_free[2];    // buffer b's last reader on the context stream
+  Event ev_in;         // the last copy into buf[cur] on the copy stream
   // the call's records so far (device), and its values (host)
-  uint64_t* d_line = nullptr;
-  uint64_t* d_start = nullptr;
-  uint64_t* d_len = nullptr;
-  uint64_t* d_voff = nullptr;  // [acc_cap + 1], DGREP_STREAM_VALUES
+  DevBuf<uint64_t> d_line, d_start, d_len;
+  DevBuf<uint64_t> d_voff;  // [acc_cap + 1], DGREP_STREAM_VALUES
   uint64_t acc_cap = 0, nrec = 0;
-  uint8_t* d_values = nullptr;  // one window's gathered lines
-  uint64_t values_cap = 0;
-  uint8_t* d_gscratch = nullptr;
-  uint64_t gscratch_cap = 0;
+  DevBuf<uint8_t> d_values;  // one window's gathered lines
+  DevBuf<uint8_t> d_gscratch;
   uint8_t* h_values = nullptr;
   uint64_t h_values_cap = 0, vbytes = 0;
   // dgrep_stream_stats
@@ -1427,13 +1218,12 @@ struct dgrep_stream {
   uint64_t line_start = 0;
   // device, one allocation: the walks' counters [2] u64, then the carried state
   // and the last walk's two verdicts, u32; pinned: the verdicts
-  unsigned long long* d_carry = nullptr;
-  uint32_t* h_verdict = nullptr;
-  uint32_t* d_pairs = nullptr;  // the walk's (guess, exit) scratch
-  uint64_t pairs_cap = 0;
-  hipEvent_t ev_w0 = nullptr, ev_w1 = nullptr;  // the last walk
-  hipEvent_t ev_v = nullptr;                     // the verdicts' copy to the host
-  bool walk_untimed = false;                     // ev_w0 / ev_w1 are recorded and not yet added to walk_ms
+  DevBuf<unsigned long long> d_carry;
+  PinnedBuf<uint32_t> h_verdict;
+  DevBuf<uint32_t> d_pairs;   // the walk's (guess, exit) scratch
+  Event ev_w0, ev_w1;         // the last walk (bounded streams only)
+  Event ev_v;                 // the verdicts' copy to the host
+  bool walk_untimed = false;  // ev_w0 / ev_w1 are recorded and not yet added to walk_ms
   uint64_t folds = 0, folded_bytes = 0, chunks = 0;
   float walk_ms = 0.f;
   // A partition stream (dgrep_stream_open_partitions, kernels/encode_window.h):
@@ -1443,14 +1233,11 @@ struct dgrep_stream {
   bool parts = false;
   uint32_t nreduce = 0;
   uint32_t key_hash0 = 0, fname_json_len = 0;
-  uint8_t* d_fname = nullptr;  // the filename, JSON-escaped
-  uint8_t* d_enc = nullptr;
-  uint64_t enc_cap = 0;
-  uint8_t* d_pscratch = nullptr;
-  uint64_t pscratch_cap = 0;
-  uint64_t* d_pbounds = nullptr;  // [2 nreduce + 2]
+  DevBuf<uint8_t> d_fname;  // the filename, JSON-escaped
+  DevBuf<uint8_t> d_enc, d_pscratch;
+  DevBuf<uint64_t> d_pbounds;  // [2 nreduce + 2]
   std::vector<uint64_t> h_pbounds;
-  hipEvent_t ev_e0 = nullptr, ev_e1 = nullptr;
+  Event ev_e0, ev_e1;  // partition streams only
   // the call's rows so far (host)
   uint8_t* h_cells = nullptr;
   uint64_t h_cells_cap = 0, cell_bytes = 0;
@@ -1462,10 +1249,9 @@ struct dgrep_stream {
   // the window route of a job (dgrep_job_*): the rows go to the job's device
   // arena and their boundaries to its segment table, nothing to the host
   dgrep_job* job = nullptr;
-  uint64_t fname_cap = 0;
 };
 
-static uint32_t* carry_state(dgrep_stream* s) { return reinterpret_cast<uint32_t*>(s->d_carry + 2); }
+static uint32_t* carry_state(dgrep_stream* s) { return reinterpret_cast<uint32_t*>(s->d_carry.p + 2); }
 static uint32_t* carry_verdict(dgrep_stream* s) { return carry_state(s) + 1; }
 
 static uint32_t sat_add32(uint32_t a, uint32_t b) { return uint32_t(std::min<uint64_t>(uint64_t(a) + b, UINT32_MAX)); }
@@ -1511,65 +1297,32 @@ static void win_stats_end(dgrep_stream* s) {
 static int win_reserve(dgrep_stream* s, int b, uint64_t need, uint64_t keep) {
   dgrep_ctx* c = s->c;
   const uint64_t want = ((need + 255) & ~uint64_t(255)) + 64;
-  if (s->buf[b] && s->cap[b] >= want) return DGREP_OK;
-  uint8_t* p = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&p), want) != hipSuccess) {
-    (void)hipGetLastError();
+  if (s->buf[b].holds(want)) return DGREP_OK;
+  // copies into the old buffer (the carried tail) are in order on the copy stream: it is drained first
+  bool nomem = false;
+  const hipError_t e = s->buf[b].regrow(want, keep, c->stream, &nomem, c->ing.copy_stream);
+  if (nomem) {
     c->err = "window buffer: out of device memory (" + std::to_string(want) + " bytes)";
     return DGREP_E_NOMEM;
   }
-  if (s->buf[b]) {
-    // copies into the old buffer (the carried tail) are in order on the copy stream
-    HIPCHK(hipStreamSynchronize(c->copy_stream));
-    if (keep) HIPCHK(hipMemcpyAsync(p, s->buf[b], keep, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipFree(s->buf[b]));
-  }
-  s->buf[b] = p;
-  s->cap[b] = want;
+  HIPCHK(e);
   return DGREP_OK;
 }
 
-// Host bytes -> dst on the copy stream, through the staging ring and the
-// dgrep_set_ingest settings as ingest() does; below the 4 MiB direct-path
-// threshold, or with chunk 0, one pageable copy. The ring may still hold the
-// window before: a staging buffer is refilled once its last DMA is done.
-// Returns with the last copy queued and s->ev_in recorded behind it.
+// The ingest with the window completion contract: host bytes -> dst, all of
+// it queued on the copy stream (ring or direct path as ingest_resident
+// chooses), no host wait beyond the ring's slot reuse. Returns with the last
+// copy queued and s->ev_in recorded behind it.
 static int win_ingest(dgrep_stream* s, uint8_t* dst, const uint8_t* src, size_t len) {
   dgrep_ctx* c = s->c;
-  if (c->ingest_chunk == 0 || len < (size_t(4) << 20)) {
-    HIPCHK(hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, c->copy_stream));
-    HIPCHK(hipEventRecord(s->ev_in, c->copy_stream));
-    return DGREP_OK;
+  IngestRing* r = &c->ing;
+  if (ingest_direct(*r, len)) {
+    INGCHK(ingest_direct_copy(r, &src, &len, 1, false, dst, len, r->copy_stream));
+  } else {
+    INGCHK(ingest_ring(r));
+    INGCHK(ingest_pieces(r, &src, &len, 1, false, dst, len));
   }
-  const size_t S = c->ingest_chunk;
-  const int B = std::max(2, c->ingest_bufs), T = std::max(1, c->ingest_threads);
-  int rc;
-  if ((rc = ingest_ring(c, S, B)) != DGREP_OK) return rc;
-  const size_t pieces = (len + S - 1) / S;
-  for (size_t k = 0; k < pieces; ++k) {
-    const int b = int(k % size_t(B));
-    const size_t off = k * S, m = std::min(S, len - off);
-    HIPCHK(hipEventSynchronize(c->ev_stage[b]));  // buffer b's last DMA is done (or it never had one)
-    uint8_t* h = c->h_stage[b];
-    const uint8_t* from = src + off;
-    if (T == 1 || m < (size_t(1) << 20)) {
-      memcpy(h, from, m);
-    } else {
-      std::vector<std::thread> th;
-      const size_t part = ((m + T - 1) / T + 4095) & ~size_t(4095);
-      for (int t = 0; t < T; ++t) {
-        const size_t a = size_t(t) * part;
-        if (a >= m) break;
-        const size_t q = std::min(part, m - a);
-        th.emplace_back([=] { memcpy(h + a, from + a, q); });
-      }
-      for (auto& x : th) x.join();
-    }
-    HIPCHK(hipMemcpyAsync(dst + off, h, m, hipMemcpyHostToDevice, c->copy_stream));
-    HIPCHK(hipEventRecord(c->ev_stage[b], c->copy_stream));
-  }
-  HIPCHK(hipEventRecord(s->ev_in, c->copy_stream));
+  HIPCHK(hipEventRecord(s->ev_in, r->copy_stream));
   return DGREP_OK;
 }
 
@@ -1579,25 +1332,23 @@ static int win_acc_reserve(dgrep_stream* s, uint64_t need) {
   if (need <= s->acc_cap) return DGREP_OK;
   const uint64_t cap = std::max<uint64_t>(need, std::max<uint64_t>(1024, 2 * s->acc_cap));
   const bool values = (s->flags & DGREP_STREAM_VALUES) != 0;
-  uint64_t* fresh[4] = {nullptr, nullptr, nullptr, nullptr};
-  uint64_t** old[4] = {&s->d_line, &s->d_start, &s->d_len, &s->d_voff};
-  for (int i = 0; i < (values ? 4 : 3); ++i) {
+  // all or nothing: the new arrays are made first, and on a failure they go and the old ones stand
+  DevBuf<uint64_t> fresh[4];
+  DevBuf<uint64_t>* old[4] = {&s->d_line, &s->d_start, &s->d_len, &s->d_voff};
+  const int arrays = values ? 4 : 3;
+  for (int i = 0; i < arrays; ++i) {
     const uint64_t extra = i == 3 ? 1 : 0;
-    if (hipMalloc(reinterpret_cast<void**>(&fresh[i]), (cap + extra) * 8) != hipSuccess) {
+    const char* what = "";
+    if (fresh[i].discard(cap + extra, &what) != hipSuccess) {
       (void)hipGetLastError();
-      for (uint64_t* f : fresh)
-        if (f) (void)hipFree(f);
       c->err = "windowed scan: out of device memory for " + std::to_string(cap) + " records";
       return DGREP_E_NOMEM;
     }
-    if (*old[i] && s->nrec)
+    if (old[i]->p && s->nrec)
       HIPCHK(hipMemcpyAsync(fresh[i], *old[i], (s->nrec + extra) * 8, hipMemcpyDeviceToDevice, c->stream));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
-  for (int i = 0; i < 4; ++i) {
-    if (*old[i]) HIPCHK(hipFree(*old[i]));
-    *old[i] = fresh[i];
-  }
+  for (int i = 0; i < arrays; ++i) old[i]->swap(fresh[i]);  // (the old arrays go with `fresh`)
   s->acc_cap = cap;
   return DGREP_OK;
 }
@@ -1666,7 +1417,7 @@ static int win_walk(dgrep_stream* s, const uint8_t* d, uint64_t m, bool want_ver
   }
   const bool rows_in_lds = uint64_t(c->pat.h_nstates) * c->pat.h_nclasses * (c->carry.u32 ? 4 : 2) <= kCarryRowsLds;
   const CarryPlan plan = carry_plan(m, carry_lanes(m, uint64_t(std::max(c->num_cus, 1)), rows_in_lds));
-  if ((rc = grow(c, &s->d_pairs, &s->pairs_cap, carry_pairs_bytes(plan) / 4)) != DGREP_OK) return rc;
+  if ((rc = grow(c, s->d_pairs, carry_pairs_bytes(plan) / 4)) != DGREP_OK) return rc;
   CarryWalk w;
   w.data = d;
   w.m = m;
@@ -1715,12 +1466,12 @@ static int win_encode(dgrep_stream* s, const uint8_t* d, uint64_t n, uint64_t co
   a.long_value = c->long_value ? c->long_value : kLongValueDefault;
   size_t need = 0;
   HIPCHK(encode_window_partitions(a, nullptr, &need, nullptr, 0, nullptr, c->stream));
-  if ((rc = grow(c, &s->d_pscratch, &s->pscratch_cap, need)) != DGREP_OK) return rc;
+  if ((rc = grow(c, s->d_pscratch, need)) != DGREP_OK) return rc;
   uint64_t total = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    size_t have = s->pscratch_cap;
+    size_t have = s->d_pscratch.cap;
     HIPCHK(hipEventRecord(s->ev_e0, c->stream));
-    HIPCHK(encode_window_partitions(a, s->d_pscratch, &have, s->d_enc, s->enc_cap, s->d_pbounds, c->stream));
+    HIPCHK(encode_window_partitions(a, s->d_pscratch, &have, s->d_enc, s->d_enc.cap, s->d_pbounds, c->stream));
     HIPCHK(hipEventRecord(s->ev_e1, c->stream));
     if (s->job)  // the totals only: the offsets stay on the device
       HIPCHK(hipMemcpyAsync(s->h_pbounds.data() + 2 * size_t(R), s->d_pbounds + 2 * size_t(R), 16,
@@ -1734,7 +1485,7 @@ static int win_encode(dgrep_stream* s, const uint8_t* d, uint64_t n, uint64_t co
     s->call_encode_ms += ms;
     s->encode_ms += ms;
     total = s->h_pbounds[2 * size_t(R)];
-    if (total <= s->enc_cap) break;
+    if (total <= s->d_enc.cap) break;
     if (attempt == 1) {
       c->err = "partition stream: the window's encoded size changed between two passes";
       return DGREP_E_HIP;
@@ -1742,7 +1493,7 @@ static int win_encode(dgrep_stream* s, const uint8_t* d, uint64_t n, uint64_t co
     // the one buffer of encoded bytes the device holds: this window's, with a sixteenth to spare
     // (a job's append kernel reads whole 16-byte vectors)
     const uint64_t want = s->job ? (total + total / 16 + 15) & ~uint64_t(15) : total + total / 16;
-    if ((rc = grow(c, &s->d_enc, &s->enc_cap, want)) != DGREP_OK) return rc;
+    if ((rc = grow(c, s->d_enc, want)) != DGREP_OK) return rc;
   }
   if (s->job) {
     ++s->rows;
@@ -1790,12 +1541,12 @@ static int win_scan(dgrep_stream* s, const uint8_t* d, uint64_t n, bool splice =
   dgrep_ctx* c = s->c;
   int rc;
   uint64_t count = 0;
-  uint64_t want = std::max<uint64_t>(c->res_cap, std::max<uint64_t>(1024, n / 512));
+  uint64_t want = std::max<uint64_t>(c->d_res_line.cap, std::max<uint64_t>(1024, n / 512));
   for (int attempt = 0; attempt < 2; ++attempt) {
     if ((rc = grow_results(c, want)) != DGREP_OK) return rc;
-    if ((rc = scan_resident(c, d, n, c->d_res_line, c->d_res_start, c->d_res_len, c->res_cap, &count)) != DGREP_OK)
+    if ((rc = scan_resident(c, d, n, c->d_res_line, c->d_res_start, c->d_res_len, c->d_res_line.cap, &count)) != DGREP_OK)
       return rc;
-    if (count <= c->res_cap) break;
+    if (count <= c->d_res_line.cap) break;
     want = count;
   }
   win_stats_add(s, n);
@@ -1834,7 +1585,7 @@ static int win_scan(dgrep_stream* s, const uint8_t* d, uint64_t n, bool splice =
       return DGREP_E_UNSUPPORTED;
     }
     // the lines lie apart in the region: their bytes sum to at most n
-    if ((rc = grow(c, &s->d_values, &s->values_cap, std::max<uint64_t>(n, 1))) != DGREP_OK) return rc;
+    if ((rc = grow(c, s->d_values, std::max<uint64_t>(n, 1))) != DGREP_OK) return rc;
     GatherArgs g;
     g.data = d;
     g.start = c->d_res_start;
@@ -1846,8 +1597,8 @@ static int win_scan(dgrep_stream* s, const uint8_t* d, uint64_t n, bool splice =
     g.total = s->d_cut + 3 * kCutBlocks + 3;
     size_t need = 0;
     HIPCHK(window_gather(g, nullptr, &need, c->num_cus, c->stream));
-    if ((rc = grow(c, &s->d_gscratch, &s->gscratch_cap, need)) != DGREP_OK) return rc;
-    size_t have = s->gscratch_cap;
+    if ((rc = grow(c, s->d_gscratch, need)) != DGREP_OK) return rc;
+    size_t have = s->d_gscratch.cap;
     HIPCHK(window_gather(g, s->d_gscratch, &have, c->num_cus, c->stream));
     HIPCHK(hipMemcpyAsync(s->h_cut + 3, g.total, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1920,13 +1671,13 @@ static int win_feed(dgrep_stream* s, const uint8_t* data, size_t n) {
       s->folded_bytes += F;
       s->max_carry = std::max(s->max_carry, s->byte_base - s->line_start);
       const int o = s->cur ^ 1;
-      HIPCHK(hipStreamWaitEvent(c->copy_stream, s->ev_free[o], 0));
+      HIPCHK(hipStreamWaitEvent(c->ing.copy_stream, s->ev_free[o], 0));
       if (next) {
         if ((rc = win_reserve(s, o, next, 0)) != DGREP_OK) return rc;
         if ((rc = win_ingest(s, s->buf[o], data + off, next)) != DGREP_OK) return rc;
         off += next;
       } else {
-        HIPCHK(hipEventRecord(s->ev_in, c->copy_stream));
+        HIPCHK(hipEventRecord(s->ev_in, c->ing.copy_stream));
       }
       s->cur = o;
       s->fill = 0;
@@ -1950,14 +1701,14 @@ static int win_feed(dgrep_stream* s, const uint8_t* data, size_t n) {
     if (s->fill && s->h_cut[2]) s->max_carry = std::max<uint64_t>(s->max_carry, s->h_cut[2] - 1);
     const int o = s->cur ^ 1;
     if ((rc = win_reserve(s, o, tail + next, 0)) != DGREP_OK) return rc;
-    HIPCHK(hipStreamWaitEvent(c->copy_stream, s->ev_free[o], 0));
+    HIPCHK(hipStreamWaitEvent(c->ing.copy_stream, s->ev_free[o], 0));
     if (tail)
-      HIPCHK(hipMemcpyAsync(s->buf[o], s->buf[s->cur] + last1, tail, hipMemcpyDeviceToDevice, c->copy_stream));
+      HIPCHK(hipMemcpyAsync(s->buf[o], s->buf[s->cur] + last1, tail, hipMemcpyDeviceToDevice, c->ing.copy_stream));
     if (next) {
       if ((rc = win_ingest(s, s->buf[o] + tail, data + off, next)) != DGREP_OK) return rc;
       off += next;
     } else {
-      HIPCHK(hipEventRecord(s->ev_in, c->copy_stream));
+      HIPCHK(hipEventRecord(s->ev_in, c->ing.copy_stream));
     }
     if (s->carrying) {
       // The carried line ends in this window, at the first '\n' (the tail holds
@@ -2023,24 +1774,13 @@ static int win_collect(dgrep_stream* s, dgrep_stream_result* out) {
   const uint64_t count = s->nrec;
   const bool values = (s->flags & DGREP_STREAM_VALUES) != 0;
   out->count = count;
-  if (count) {
-    out->line_no = static_cast<uint64_t*>(malloc(count * 8));
-    out->start = static_cast<uint64_t*>(malloc(count * 8));
-    out->len = static_cast<uint64_t*>(malloc(count * 8));
-  }
-  if (values) out->value_off = static_cast<uint64_t*>(malloc((count + 1) * 8));
-  if ((count && (!out->line_no || !out->start || !out->len)) || (values && !out->value_off)) {
-    dgrep_stream_result_free(out);
-    return DGREP_E_NOMEM;
-  }
-  if (count) {
-    HIPCHK(hipMemcpyAsync(out->line_no, s->d_line, count * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(out->start, s->d_start, count * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(out->len, s->d_len, count * 8, hipMemcpyDeviceToHost, c->stream));
-    if (values)
-      HIPCHK(hipMemcpyAsync(out->value_off + 1, s->d_voff + 1, count * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
+  const size_t b = count * 8;
+  const int rc = fetch_results(c, {{&out->line_no, s->d_line, b, 0},
+                                   {&out->start, s->d_start, b, 0},
+                                   {&out->len, s->d_len, b, 0},
+                                   {&out->value_off, s->d_voff.p ? s->d_voff + 1 : nullptr, values ? b : 0, values ? 8u : 0u}});
+  if (rc == DGREP_E_NOMEM) dgrep_stream_result_free(out);
+  if (rc != DGREP_OK) return rc;
   if (values) {
     out->value_off[0] = 0;
     out->values = s->h_values;
@@ -2063,20 +1803,20 @@ static int win_open(dgrep_ctx* c, size_t window_bytes, uint32_t flags, dgrep_str
   s->flags = flags;
   s->gen = c->load_gen;
   *out = s;  // kept on failure too: dgrep_stream_close frees what was made
-  if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->d_cut), (3 * kCutBlocks + 4) * sizeof(unsigned long long)));
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_cut), 4 * sizeof(unsigned long long), hipHostMallocDefault));
-  HIPCHK(hipEventCreate(&s->ev_c0));
-  HIPCHK(hipEventCreate(&s->ev_c1));
-  for (hipEvent_t* e : {&s->ev_free[0], &s->ev_free[1], &s->ev_in})
-    HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  int rc;
+  HIPCHK(c->ing.copy_stream.create());
+  if ((rc = grow(c, s->d_cut, 3 * kCutBlocks + 4)) != DGREP_OK) return rc;
+  HIPCHK(s->h_cut.alloc(4));
+  HIPCHK(s->ev_c0.create());
+  HIPCHK(s->ev_c1.create());
+  for (Event* e : {&s->ev_free[0], &s->ev_free[1], &s->ev_in}) HIPCHK(e->create(hipEventDisableTiming));
   if (flags & DGREP_STREAM_BOUNDED) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->d_carry), 32));
+    if ((rc = grow(c, s->d_carry, 4)) != DGREP_OK) return rc;
     HIPCHK(hipMemsetAsync(s->d_carry, 0, 32, c->stream));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_verdict), 2 * sizeof(uint32_t), hipHostMallocDefault));
-    HIPCHK(hipEventCreate(&s->ev_w0));
-    HIPCHK(hipEventCreate(&s->ev_w1));
-    HIPCHK(hipEventCreateWithFlags(&s->ev_v, hipEventDisableTiming));
+    HIPCHK(s->h_verdict.alloc(2));
+    HIPCHK(s->ev_w0.create());
+    HIPCHK(s->ev_w1.create());
+    HIPCHK(s->ev_v.create(hipEventDisableTiming));
   }
   return DGREP_OK;
 }
@@ -2085,17 +1825,8 @@ extern "C" void dgrep_stream_close(dgrep_stream* s) {
   if (!s) return;
   dgrep_ctx* c = s->c;
   (void)hipSetDevice(c->device);
-  if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+  if (c->ing.copy_stream) (void)hipStreamSynchronize(c->ing.copy_stream);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  void* bufs[] = {s->buf[0], s->buf[1], s->d_cut, s->d_line, s->d_start, s->d_len, s->d_voff, s->d_values, s->d_gscratch,
-                  s->d_carry, s->d_pairs, s->d_fname, s->d_enc, s->d_pscratch, s->d_pbounds};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  if (s->h_cut) (void)hipHostFree(s->h_cut);
-  if (s->h_verdict) (void)hipHostFree(s->h_verdict);
-  for (hipEvent_t e : {s->ev_c0, s->ev_c1, s->ev_free[0], s->ev_free[1], s->ev_in, s->ev_w0, s->ev_w1, s->ev_v,
-                       s->ev_e0, s->ev_e1})
-    if (e) (void)hipEventDestroy(e);
   free(s->h_values);
   free(s->h_cells);
   delete s;
@@ -2173,7 +1904,7 @@ static int win_fail(dgrep_stream* s, int rc) {
   dgrep_ctx* c = s->c;
   const std::string msg = c->err;
   s->status = rc;
-  if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+  if (c->ing.copy_stream) (void)hipStreamSynchronize(c->ing.copy_stream);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   (void)hipGetLastError();
   c->err = msg;
@@ -2224,7 +1955,7 @@ extern "C" int dgrep_stream_stats(dgrep_stream* s, uint64_t* windows, uint64_t* 
                                   float* cut_ms) {
   if (!s) return DGREP_E_INVALID;
   if (windows) *windows = s->windows;
-  if (data_bytes) *data_bytes = s->cap[0] + s->cap[1];
+  if (data_bytes) *data_bytes = s->buf[0].cap + s->buf[1].cap;
   if (max_carry) *max_carry = s->max_carry;
   if (cut_ms) *cut_ms = s->cut_ms;
   return DGREP_OK;
@@ -2347,12 +2078,12 @@ static int win_open_parts(dgrep_ctx* c, size_t window_bytes, const char* filenam
   json_escape_host(fname, fn, fjson.data());
   s->fname_json_len = uint32_t(fj);
   s->key_hash0 = key_prefix_hash(fname, fn);
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->d_fname), fj + 1));
+  if ((rc = grow(c, s->d_fname, fj + 1)) != DGREP_OK) return rc;
   HIPCHK(hipMemcpy(s->d_fname, fjson.data(), fj + 1, hipMemcpyHostToDevice));
   s->h_pbounds.assign(2 * size_t(nreduce) + 2, 0);
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->d_pbounds), s->h_pbounds.size() * 8));
-  HIPCHK(hipEventCreate(&s->ev_e0));
-  HIPCHK(hipEventCreate(&s->ev_e1));
+  if ((rc = grow(c, s->d_pbounds, s->h_pbounds.size())) != DGREP_OK) return rc;
+  HIPCHK(s->ev_e0.create());
+  HIPCHK(s->ev_e1.create());
   return DGREP_OK;
 }
 
@@ -2425,7 +2156,7 @@ extern "C" int dgrep_stream_partition_stats(dgrep_stream* s, uint64_t* rows, uin
   if (rows) *rows = s->rows;
   if (out_bytes) *out_bytes = s->out_bytes;
   if (long_values) *long_values = s->long_values;
-  if (enc_device_bytes) *enc_device_bytes = s->enc_cap;
+  if (enc_device_bytes) *enc_device_bytes = s->d_enc.cap;
   if (encode_ms) *encode_ms = s->encode_ms;
   return DGREP_OK;
 }
@@ -2470,9 +2201,9 @@ static int encode_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, cons
   if (fj >= (uint64_t(1) << 31)) { c->err = "filename too long"; return DGREP_E_INVALID; }
   std::vector<uint8_t> fjson(fj + 1);
   json_escape_host(fname, fn, fjson.data());
-  if ((rc = grow(c, &c->d_fname, &c->fname_cap, fj + 1)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_fname, fj + 1)) != DGREP_OK) return rc;
   HIPCHK(hipMemcpyAsync(c->d_fname, fjson.data(), fj + 1, hipMemcpyHostToDevice, c->stream));
-  if ((rc = grow(c, &c->d_bounds, &c->bounds_cap, 2 * uint64_t(nreduce) + 3)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_bounds, 2 * uint64_t(nreduce) + 3)) != DGREP_OK) return rc;
   EncodeArgs a;
   a.data = d_data;
   a.n = n;
@@ -2487,8 +2218,8 @@ static int encode_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, cons
   const uint32_t long_value = c->long_value ? c->long_value : kLongValueResidentDefault;
   size_t need = 0;
   HIPCHK(encode_partitions(a, long_value, nullptr, &need, nullptr, 0, nullptr, c->stream));
-  if ((rc = grow(c, &c->d_enc_scratch, &c->enc_scratch_cap, need)) != DGREP_OK) return rc;
-  size_t have = c->enc_scratch_cap;
+  if ((rc = grow(c, c->d_enc_scratch, need)) != DGREP_OK) return rc;
+  size_t have = c->d_enc_scratch.cap;
   HIPCHK(hipEventRecord(c->ev0, c->stream));
   HIPCHK(encode_partitions(a, long_value, c->d_enc_scratch, &have, d_out, out_cap, c->d_bounds, c->stream));
   HIPCHK(hipEventRecord(c->ev1, c->stream));
@@ -2532,17 +2263,17 @@ extern "C" int dgrep_map_partitions(dgrep_ctx* c, const uint8_t* data, size_t n,
   out->begin = static_cast<uint64_t*>(calloc(nreduce, 8));
   out->end = static_cast<uint64_t*>(calloc(nreduce, 8));
   if (!out->begin || !out->end) { dgrep_partitions_free(out); return DGREP_E_NOMEM; }
-  const uint8_t* dd = c->d_data ? c->d_data : reinterpret_cast<const uint8_t*>(c->d_counters);
+  const uint8_t* dd = c->d_data ? c->d_data : reinterpret_cast<const uint8_t*>(c->d_counters.p);
   uint64_t total = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
     if ((rc = encode_resident(c, dd, c->d_data ? n : 0, c->d_res_line, c->d_res_start, c->d_res_len, count, filename,
                               fn, nreduce,
-                              c->d_enc_out, c->enc_out_cap, out->begin, out->end, &total)) != DGREP_OK) {
+                              c->d_enc_out, c->d_enc_out.cap, out->begin, out->end, &total)) != DGREP_OK) {
       dgrep_partitions_free(out);
       return rc;
     }
-    if (total <= c->enc_out_cap) break;
-    if ((rc = grow(c, &c->d_enc_out, &c->enc_out_cap, total + total / 16)) != DGREP_OK) {
+    if (total <= c->d_enc_out.cap) break;
+    if ((rc = grow(c, c->d_enc_out, total + total / 16)) != DGREP_OK) {
       dgrep_partitions_free(out);
       return rc;
     }
@@ -2616,8 +2347,8 @@ static int encode_batch_resident(dgrep_ctx* c, const uint8_t* d_packed, uint64_t
     return DGREP_OK;
   }
   int rc;
-  if ((rc = grow(c, &c->d_bat_names, &c->bat_names_cap, names.size())) != DGREP_OK) return rc;
-  if ((rc = grow(c, &c->d_bat_cells, &c->bat_cells_cap, cells + 3)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_bat_names, names.size())) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_bat_cells, cells + 3)) != DGREP_OK) return rc;
   HIPCHK(hipMemcpyAsync(c->d_bat_begin, c->bat_begin.data(), (k + 1) * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->d_bat_names, names.data(), names.size(), hipMemcpyHostToDevice, c->stream));
   EncodeBatchArgs a;
@@ -2630,15 +2361,15 @@ static int encode_batch_resident(dgrep_ctx* c, const uint8_t* d_packed, uint64_t
   a.len = d_len;
   a.split = d_split;
   a.count = count;
-  a.name_off = reinterpret_cast<const uint64_t*>(c->d_bat_names);
+  a.name_off = reinterpret_cast<const uint64_t*>(c->d_bat_names.p);
   a.name_hash = reinterpret_cast<const uint32_t*>(c->d_bat_names + (k + 1) * 8);
   a.names = c->d_bat_names + (k + 1) * 8 + k * 4;
   a.nreduce = nreduce;
   const uint32_t long_value = c->long_value ? c->long_value : kLongValueResidentDefault;
   size_t need = 0;
   HIPCHK(encode_batch(a, long_value, nullptr, &need, nullptr, 0, nullptr, c->stream));
-  if ((rc = grow(c, &c->d_enc_scratch, &c->enc_scratch_cap, need)) != DGREP_OK) return rc;
-  size_t have = c->enc_scratch_cap;
+  if ((rc = grow(c, c->d_enc_scratch, need)) != DGREP_OK) return rc;
+  size_t have = c->d_enc_scratch.cap;
   HIPCHK(hipEventRecord(c->ev0, c->stream));
   HIPCHK(encode_batch(a, long_value, c->d_enc_scratch, &have, d_out, out_cap, c->d_bat_cells, c->stream));
   HIPCHK(hipEventRecord(c->ev1, c->stream));
@@ -2733,13 +2464,13 @@ extern "C" int dgrep_map_partitions_batch(dgrep_ctx* c, const uint8_t* const* da
   uint64_t total = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
     if ((rc = encode_batch_resident(c, c->d_data, total_in, nsplits, c->d_res_line, c->d_res_start, c->d_res_len,
-                                    c->d_res_split, count, names, nreduce, c->d_enc_out, c->enc_out_cap,
+                                    c->d_res_split, count, names, nreduce, c->d_enc_out, c->d_enc_out.cap,
                                     out->cell_off, &total)) != DGREP_OK) {
       dgrep_batch_partitions_free(out);
       return rc;
     }
-    if (total <= c->enc_out_cap) break;
-    if ((rc = grow(c, &c->d_enc_out, &c->enc_out_cap, total + total / 16)) != DGREP_OK) {
+    if (total <= c->d_enc_out.cap) break;
+    if ((rc = grow(c, c->d_enc_out, total + total / 16)) != DGREP_OK) {
       dgrep_batch_partitions_free(out);
       return rc;
     }
@@ -2770,11 +2501,9 @@ extern "C" int dgrep_reduce(dgrep_ctx* c, const uint8_t* data, size_t n, dgrep_r
   HIPCHK(hipSetDevice(c->device));
   if (n == 0) return DGREP_OK;
   int rc;
-  uint64_t cap = c->data_cap;
-  if ((rc = grow(c, &c->d_data, &cap, (n + 63) & ~uint64_t(63))) != DGREP_OK) return rc;
-  c->data_cap = cap;
-  if ((rc = ingest(c, data, n)) != DGREP_OK) return rc;
-  uint64_t* d_info = reinterpret_cast<uint64_t*>(c->d_counters);  // 3 of its 4 u64
+  if ((rc = grow(c, c->d_data, (n + 63) & ~uint64_t(63))) != DGREP_OK) return rc;
+  if ((rc = ingest_resident(c, &data, &n, 1, n)) != DGREP_OK) return rc;
+  uint64_t* d_info = reinterpret_cast<uint64_t*>(c->d_counters.p);  // 3 of its 4 u64
   HIPCHK(reduce_count_lines(c->d_data, n, d_info, c->stream));
   uint64_t nlines = 0;
   HIPCHK(hipMemcpyAsync(&nlines, d_info, 8, hipMemcpyDeviceToHost, c->stream));
@@ -2785,12 +2514,12 @@ extern "C" int dgrep_reduce(dgrep_ctx* c, const uint8_t* data, size_t n, dgrep_r
   }
   size_t need = 0;
   HIPCHK(reduce_lines(c->d_data, n, nlines, nullptr, &need, nullptr, 0, d_info, c->stream));
-  if ((rc = grow(c, &c->d_red_scratch, &c->red_scratch_cap, need)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_red_scratch, need)) != DGREP_OK) return rc;
   uint64_t info[3] = {0, 0, 0};
   for (int attempt = 0; attempt < 2; ++attempt) {
-    size_t have = c->red_scratch_cap;
+    size_t have = c->d_red_scratch.cap;
     HIPCHK(hipEventRecord(c->ev0, c->stream));
-    HIPCHK(reduce_lines(c->d_data, n, nlines, c->d_red_scratch, &have, c->d_red_out, c->red_out_cap, d_info,
+    HIPCHK(reduce_lines(c->d_data, n, nlines, c->d_red_scratch, &have, c->d_red_out, c->d_red_out.cap, d_info,
                         c->stream));
     HIPCHK(hipEventRecord(c->ev1, c->stream));
     HIPCHK(hipMemcpyAsync(info, d_info, sizeof info, hipMemcpyDeviceToHost, c->stream));
@@ -2799,8 +2528,8 @@ extern "C" int dgrep_reduce(dgrep_ctx* c, const uint8_t* data, size_t n, dgrep_r
       c->err = "reduce input line " + std::to_string(info[1] + 1) + " is not a {\"Key\":\"..\",\"Value\":\"..\"} line";
       return DGREP_E_INVALID;
     }
-    if (info[2] <= c->red_out_cap) break;
-    if ((rc = grow(c, &c->d_red_out, &c->red_out_cap, info[2])) != DGREP_OK) return rc;
+    if (info[2] <= c->d_red_out.cap) break;
+    if ((rc = grow(c, c->d_red_out, info[2])) != DGREP_OK) return rc;
   }
   HIPCHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
   out->lines_in = info[0];
@@ -2839,9 +2568,8 @@ static int reduce_batch_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n
     return DGREP_E_INVALID;
   }
   int rc;
-  if ((rc = grow(c, &c->d_rb_off, &c->rb_off_cap, 2 * uint64_t(nparts) + 1)) != DGREP_OK) return rc;
-  for (hipEvent_t* e : {&c->evr0, &c->evr1})
-    if (!*e) HIPCHK(hipEventCreate(e));
+  if ((rc = grow(c, c->d_rb_off, 2 * uint64_t(nparts) + 1)) != DGREP_OK) return rc;
+  for (Event* e : {&c->evr0, &c->evr1}) HIPCHK(e->create());
   ReduceBatchArgs a;
   a.data = d_data;
   a.n = n;
@@ -2849,13 +2577,13 @@ static int reduce_batch_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n
   a.nseg = nseg;
   a.nparts = nparts;
   a.nlines = nlines;
-  uint64_t* d_info = reinterpret_cast<uint64_t*>(c->d_counters);  // 3 of its u64
+  uint64_t* d_info = reinterpret_cast<uint64_t*>(c->d_counters.p);  // 3 of its u64
   uint64_t* d_part_off = c->d_rb_off;
   uint64_t* d_lines_in = c->d_rb_off + nparts + 1;
   size_t need = 0;
   HIPCHK(reduce_batch(a, nullptr, &need, nullptr, 0, nullptr, nullptr, d_info, c->stream));
-  if ((rc = grow(c, &c->d_red_scratch, &c->red_scratch_cap, need)) != DGREP_OK) return rc;
-  size_t have = c->red_scratch_cap;
+  if ((rc = grow(c, c->d_red_scratch, need)) != DGREP_OK) return rc;
+  size_t have = c->d_red_scratch.cap;
   uint64_t info[3] = {0, 0, 0};
   HIPCHK(hipEventRecord(c->evr0, c->stream));
   HIPCHK(reduce_batch(a, c->d_red_scratch, &have, d_out, out_cap, d_part_off, d_lines_in, d_info, c->stream));
@@ -2884,7 +2612,7 @@ static int reduce_batch_resident(dgrep_ctx* c, const uint8_t* d_data, uint64_t n
 
 // the '\n' in d_data[0:n): one kernel and one host wait
 static int reduce_count_host(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, uint64_t* nlines) {
-  uint64_t* d_info = reinterpret_cast<uint64_t*>(c->d_counters);
+  uint64_t* d_info = reinterpret_cast<uint64_t*>(c->d_counters.p);
   *nlines = 0;
   if (n == 0) return DGREP_OK;
   HIPCHK(reduce_count_lines(d_data, n, d_info, c->stream));
@@ -2911,11 +2639,11 @@ static int reduce_batch_owned(dgrep_ctx* c, const uint8_t* d_data, uint64_t n, c
   int rc;
   uint64_t total = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if ((rc = reduce_batch_resident(c, d_data, n, d_seg, nseg, nparts, nlines, c->d_red_out, c->red_out_cap,
+    if ((rc = reduce_batch_resident(c, d_data, n, d_seg, nseg, nparts, nlines, c->d_red_out, c->d_red_out.cap,
                                     out->part_off, out->lines_in, &total)) != DGREP_OK)
       return rc;
-    if (total <= c->red_out_cap) break;
-    if ((rc = grow(c, &c->d_red_out, &c->red_out_cap, total)) != DGREP_OK) return rc;
+    if (total <= c->d_red_out.cap) break;
+    if ((rc = grow(c, c->d_red_out, total)) != DGREP_OK) return rc;
   }
   return reduce_batch_fetch(c, total, out);
 }
@@ -2952,13 +2680,11 @@ extern "C" int dgrep_reduce_batch(dgrep_ctx* c, const uint8_t* const* data, cons
   };
   if (hipError_t e = hipSetDevice(c->device); e != hipSuccess) return fail(hip_fail(c, e, "hipSetDevice"));
   int rc;
-  uint64_t cap = c->data_cap;
-  if ((rc = grow(c, &c->d_data, &cap, (uint64_t(total_in) + 63) & ~uint64_t(63))) != DGREP_OK) return fail(rc);
-  c->data_cap = cap;
-  if ((rc = ingest_packed(c, data, n, nparts, total_in, false)) != DGREP_OK) return fail(rc);
+  if ((rc = grow(c, c->d_data, (uint64_t(total_in) + 63) & ~uint64_t(63))) != DGREP_OK) return fail(rc);
+  if ((rc = ingest_resident(c, data, n, nparts, total_in, false)) != DGREP_OK) return fail(rc);
   std::vector<uint64_t> seg(nparts + 1, 0);
   for (size_t p = 0; p < nparts; ++p) seg[p + 1] = seg[p] + n[p];
-  if ((rc = grow(c, &c->d_rb_seg, &c->rb_seg_cap, nparts + 1)) != DGREP_OK) return fail(rc);
+  if ((rc = grow(c, c->d_rb_seg, nparts + 1)) != DGREP_OK) return fail(rc);
   if (hipError_t e = hipMemcpyAsync(c->d_rb_seg, seg.data(), (nparts + 1) * 8, hipMemcpyHostToDevice, c->stream);
       e != hipSuccess)
     return fail(hip_fail(c, e, "hipMemcpyAsync"));
@@ -3008,7 +2734,7 @@ extern "C" int dgrep_reduce_batch_device(dgrep_ctx* c, const void* d_data, size_
   }
   HIPCHK(hipSetDevice(c->device));
   int rc;
-  if ((rc = grow(c, &c->d_rb_seg, &c->rb_seg_cap, uint64_t(nseg) + 1)) != DGREP_OK) return rc;
+  if ((rc = grow(c, c->d_rb_seg, uint64_t(nseg) + 1)) != DGREP_OK) return rc;
   HIPCHK(hipMemcpyAsync(c->d_rb_seg, seg_off, (uint64_t(nseg) + 1) * 8, hipMemcpyHostToDevice, c->stream));
   uint64_t nlines = 0;
   if ((rc = reduce_count_host(c, static_cast<const uint8_t*>(d_data), n, &nlines)) != DGREP_OK) return rc;
@@ -3053,11 +2779,11 @@ extern "C" int dgrep_grep_job(dgrep_ctx* c, const uint8_t* const* data, const si
   uint64_t enc_total = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
     if ((rc = encode_batch_resident(c, c->d_data, total_in, nsplits, c->d_res_line, c->d_res_start, c->d_res_len,
-                                    c->d_res_split, count, names, nreduce, c->d_enc_out, c->enc_out_cap, nullptr,
+                                    c->d_res_split, count, names, nreduce, c->d_enc_out, c->d_enc_out.cap, nullptr,
                                     &enc_total)) != DGREP_OK)
       return fail(rc);
-    if (enc_total <= c->enc_out_cap) break;
-    if ((rc = grow(c, &c->d_enc_out, &c->enc_out_cap, enc_total + enc_total / 16)) != DGREP_OK) return fail(rc);
+    if (enc_total <= c->d_enc_out.cap) break;
+    if ((rc = grow(c, c->d_enc_out, enc_total + enc_total / 16)) != DGREP_OK) return fail(rc);
   }
   // one KeyValue line per record; the scratch is sized by the '\n' actually there
   uint64_t nlines = 0;
@@ -3094,11 +2820,10 @@ struct dgrep_job {
   std::vector<size_t> pack_off, pack_len;
   std::vector<std::string> pack_name;
   // the arena and the segment table (device); plan.used bytes and plan.nseg + 1 entries are valid
-  uint8_t* d_arena = nullptr;
-  uint64_t arena_cap = 0, arena_growths = 0;
-  uint64_t* d_seg = nullptr;
-  uint64_t seg_cap = 0;
-  hipEvent_t ev_a0 = nullptr, ev_a1 = nullptr;  // the last append
+  DevBuf<uint8_t> d_arena;
+  uint64_t arena_growths = 0;
+  DevBuf<uint64_t> d_seg;
+  Event ev_a0, ev_a1;  // the last append
   bool append_untimed = false;
   float append_ms = 0.f, reduce_ms = 0.f;
 };
@@ -3118,24 +2843,17 @@ static int job_append_ms_take(dgrep_job* j) {
 // *p holds `need` units of T; the first `keep` survive. Old and new buffer
 // exist together for the one device copy.
 template <class T>
-static int job_grow(dgrep_job* j, T** p, uint64_t* cap, uint64_t need, uint64_t keep, uint64_t initial,
-                    const char* what) {
+static int job_grow(dgrep_job* j, DevBuf<T>& b, uint64_t need, uint64_t keep, uint64_t initial, const char* what) {
   dgrep_ctx* c = j->c;
-  if (*p && *cap >= need) return DGREP_OK;
-  const uint64_t want = job_grow_cap(*p ? *cap : 0, need, initial);
-  T* fresh = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&fresh), want * sizeof(T)) != hipSuccess) {
-    (void)hipGetLastError();
+  if (b.holds(need)) return DGREP_OK;
+  const uint64_t want = job_grow_cap(b.cap, need, initial);
+  bool nomem = false;
+  const hipError_t e = b.regrow(want, keep, c->stream, &nomem);  // (its wait: the copy, and every append into the old buffer)
+  if (nomem) {
     c->err = std::string("job ") + what + ": out of device memory (" + std::to_string(want * sizeof(T)) + " bytes)";
     return DGREP_E_NOMEM;
   }
-  if (*p) {
-    if (keep) HIPCHK(hipMemcpyAsync(fresh, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));  // the copy, and every append into the old buffer
-    HIPCHK(hipFree(*p));
-  }
-  *p = fresh;
-  *cap = want;
+  HIPCHK(e);
   return DGREP_OK;
 }
 
@@ -3151,14 +2869,14 @@ static int job_append_rows(dgrep_job* j, const uint8_t* d_src, uint64_t total, c
     return DGREP_E_UNSUPPORTED;
   }
   int rc;
-  const bool first = j->d_seg == nullptr;
-  const uint64_t had = j->arena_cap;
+  const bool first = j->d_seg.p == nullptr;
+  const uint64_t had = j->d_arena.cap;
   // (the reduce reads whole 16-byte vectors: the capacity is a multiple of 16)
-  if ((rc = job_grow(j, &j->d_arena, &j->arena_cap, (at + total + 15) & ~uint64_t(15), used0, kJobArenaInitial,
+  if ((rc = job_grow(j, j->d_arena, (at + total + 15) & ~uint64_t(15), used0, kJobArenaInitial,
                      "arena")) != DGREP_OK)
     return rc;
-  if (had && j->arena_cap != had) ++j->arena_growths;
-  if ((rc = job_grow(j, &j->d_seg, &j->seg_cap, j->plan.nseg + 1, nseg0 + 1, kJobSegInitial, "segment table")) !=
+  if (had && j->d_arena.cap != had) ++j->arena_growths;
+  if ((rc = job_grow(j, j->d_seg, j->plan.nseg + 1, nseg0 + 1, kJobSegInitial, "segment table")) !=
       DGREP_OK)
     return rc;
   if (first) HIPCHK(hipMemsetAsync(j->d_seg, 0, 8, c->stream));  // seg_off[0] = 0
@@ -3210,17 +2928,17 @@ static int job_flush(dgrep_job* j) {
   uint64_t enc_total = 0;
   for (int attempt = 0; attempt < 2; ++attempt) {
     if ((rc = encode_batch_resident(c, c->d_data, bytes, k, c->d_res_line, c->d_res_start, c->d_res_len, c->d_res_split,
-                                    count, names, j->plan.nreduce, c->d_enc_out, c->enc_out_cap, nullptr,
+                                    count, names, j->plan.nreduce, c->d_enc_out, c->d_enc_out.cap, nullptr,
                                     &enc_total)) != DGREP_OK)
       return rc;
     j->s->call_encode_ms += c->last_encode_ms;
     // (the append kernel reads whole 16-byte vectors)
-    if (enc_total <= c->enc_out_cap && ((enc_total + 15) & ~uint64_t(15)) <= c->enc_out_cap) break;
+    if (enc_total <= c->d_enc_out.cap && ((enc_total + 15) & ~uint64_t(15)) <= c->d_enc_out.cap) break;
     if (attempt == 1) {
       c->err = "job: the pack's encoded size changed between two passes";
       return DGREP_E_HIP;
     }
-    if ((rc = grow(c, &c->d_enc_out, &c->enc_out_cap, (enc_total + enc_total / 16 + 15) & ~uint64_t(15))) != DGREP_OK)
+    if ((rc = grow(c, c->d_enc_out, (enc_total + enc_total / 16 + 15) & ~uint64_t(15))) != DGREP_OK)
       return rc;
   }
   j->enc_sum.records += c->enc_stats.records;  // the pack's last attempt
@@ -3239,7 +2957,7 @@ static int job_file_start(dgrep_job* j, const char* filename, size_t fn) {
   std::vector<uint8_t> fjson(fj + 1);
   json_escape_host(fname, fn, fjson.data());
   int rc;
-  if ((rc = grow(c, &s->d_fname, &s->fname_cap, fj + 1)) != DGREP_OK) return rc;
+  if ((rc = grow(c, s->d_fname, fj + 1)) != DGREP_OK) return rc;
   HIPCHK(hipMemcpy(s->d_fname, fjson.data(), fj + 1, hipMemcpyHostToDevice));
   s->fname_json_len = uint32_t(fj);
   s->key_hash0 = key_prefix_hash(fname, fn);
@@ -3271,7 +2989,7 @@ static int job_fail(dgrep_job* j, int rc) {
   dgrep_ctx* c = j->c;
   const std::string msg = c->err;
   j->status = rc;
-  if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+  if (c->ing.copy_stream) (void)hipStreamSynchronize(c->ing.copy_stream);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   (void)hipGetLastError();
   c->err = msg;
@@ -3284,16 +3002,12 @@ extern "C" void dgrep_job_close(dgrep_job* j) {
   (void)hipSetDevice(c->device);
   if (j->s) dgrep_stream_close(j->s);  // (waits for both streams)
   else if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (j->d_arena) (void)hipFree(j->d_arena);
-  if (j->d_seg) (void)hipFree(j->d_seg);
   if (j->pack && !c->h_job_pack) {  // kept for the context's next job
     c->h_job_pack = j->pack;
     c->h_job_pack_cap = j->pack_cap;
   } else {
     free(j->pack);
   }
-  for (hipEvent_t e : {j->ev_a0, j->ev_a1})
-    if (e) (void)hipEventDestroy(e);
   delete j;
 }
 
@@ -3315,8 +3029,8 @@ static int job_open(dgrep_ctx* c, size_t window_bytes, uint32_t nreduce, dgrep_j
   s->nreduce = nreduce;
   s->job = j;
   s->h_pbounds.assign(2 * size_t(nreduce) + 2, 0);
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s->d_pbounds), s->h_pbounds.size() * 8));
-  for (hipEvent_t* e : {&s->ev_e0, &s->ev_e1, &j->ev_a0, &j->ev_a1}) HIPCHK(hipEventCreate(e));
+  if ((rc = grow(c, s->d_pbounds, s->h_pbounds.size())) != DGREP_OK) return rc;
+  for (Event* e : {&s->ev_e0, &s->ev_e1, &j->ev_a0, &j->ev_a1}) HIPCHK(e->create());
   win_stats_begin(s);  // the scan stats and the encode time are summed over the job
   return DGREP_OK;
 }
@@ -3376,21 +3090,7 @@ extern "C" int dgrep_job_add(dgrep_job* j, const uint8_t* data, size_t n, const 
     j->pack_cap = cap;
   }
   if (off) j->pack[off - 1] = uint8_t('\n');
-  const int T = std::max(1, c->ingest_threads);
-  if (T == 1 || n < (size_t(1) << 20)) {
-    if (n) memcpy(j->pack + off, data, n);
-  } else {  // as the ingest copies a large piece: by its CPU threads
-    std::vector<std::thread> th;
-    const size_t part = ((n + T - 1) / T + 4095) & ~size_t(4095);
-    uint8_t* dst = j->pack + off;
-    for (int t = 0; t < T; ++t) {
-      const size_t a = size_t(t) * part;
-      if (a >= n) break;
-      const size_t m = std::min(part, n - a);
-      th.emplace_back([=] { memcpy(dst + a, data + a, m); });
-    }
-    for (auto& x : th) x.join();
-  }
+  pack_copy_threaded(j->pack + off, data, n, std::max(1, c->ing.threads));  // as the ingest copies a large piece
   j->pack_off.push_back(off);
   j->pack_len.push_back(n);
   j->pack_name.emplace_back(filename ? filename : "", fn);
@@ -3497,8 +3197,8 @@ extern "C" int dgrep_job_stats_get(dgrep_job* j, dgrep_job_stats* out, size_t ou
   st.rows = j->plan.rows;
   st.segments = j->plan.nseg;
   st.arena_bytes = j->plan.used;
-  st.arena_device_bytes = j->arena_cap;
-  st.window_device_bytes = s->cap[0] + s->cap[1];
+  st.arena_device_bytes = j->d_arena.cap;
+  st.window_device_bytes = s->buf[0].cap + s->buf[1].cap;
   st.long_values = s->long_values;
   st.arena_growths = j->arena_growths;
   st.scan_ms = s->agg_ms;

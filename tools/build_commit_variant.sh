@@ -17,8 +17,9 @@ make -s -C "$P" >/dev/null
 $HIPCC $FLAGS -c "$W/distributed-grep_amd/csrc/kernels/scan_dfa.hip" -o "$P/build/scan_dfa_c_$NAME.o" 2> "$P/build/variant_$NAME.log" &
 $HIPCC $FLAGS -c "$W/distributed-grep_amd/csrc/runtime/dgrep_runtime.hip" -o "$P/build/dgrep_runtime_c_$NAME.o" 2>> "$P/build/variant_$NAME.log" &
 wait %1 && wait %2
-$HIPCC -shared -fPIC --offload-arch=gfx950 -o "$P/variants/libdgrep_$NAME.so" "$P"/build/go_parser.o "$P"/build/dfa_builder.o \
-  "$P"/build/compile_api.o "$P/build/scan_dfa_c_$NAME.o" "$P"/build/encode.o "$P"/build/reduce.o "$P/build/dgrep_runtime_c_$NAME.o" \
-  "$P"/build/exchange.o "$P"/build/build_info.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+# every other object of the current build: all but its scan parts, its runtime and other variants' objects
+REST=$(ls "$P"/build/*.o | grep -v -e '/scan_dfa_' -e '/dgrep_runtime')
+$HIPCC -shared -fPIC --offload-arch=gfx950 -o "$P/variants/libdgrep_$NAME.so" "$P/build/scan_dfa_c_$NAME.o" \
+  "$P/build/dgrep_runtime_c_$NAME.o" $REST -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 git -C "$R" worktree remove --force "$W"
 echo "built $NAME from $COMMIT"
