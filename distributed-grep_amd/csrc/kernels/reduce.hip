@@ -68,9 +68,7 @@ __global__ __launch_bounds__(kRT) void dedupe_kernel(const uint8_t* s, const uin
     bool keep = !any_bad;
     for (uint64_t p = q; keep && p-- > 0 && h_sorted[p] == h_sorted[q];) {
       const uint32_t k = idx_sorted[p];
-      // Equal 64-bit hashes of different keys: no test can construct two such
-      // keys, so this `continue` and the `same = false` of the decoded compare
-      // below are covered by reading alone.
+      // different keys with one 64-bit hash take every "no" below: tests/test_gpu_reduce_collisions.py
       if (klen[k] != klen[j]) continue;
       const uint64_t aj = j ? nl[j - 1] + 1 : 0, ak = k ? nl[k - 1] + 1 : 0;
       bool same = true;

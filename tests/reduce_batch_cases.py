@@ -6,6 +6,7 @@ partition's concatenated input at a time."""
 import random
 from collections import namedtuple
 
+import fnv64_collisions as F
 import go_json as G
 import reduce_cases as R
 
@@ -170,6 +171,8 @@ def good_cases():
         sparse_65535(), kept_runs(), phases(), new_rules(),
         block_edge(-1), block_edge(0), block_edge(1),
     ]
+    # different keys with one 64-bit hash, within and across partitions (fnv64_collisions.py)
+    cases += [from_segments(name, segs, nparts) for name, segs, nparts in F.batch_segments()]
     return cases
 
 

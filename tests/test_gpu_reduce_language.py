@@ -76,6 +76,9 @@ def test_spellings_merge_across_64_bytes(gpu_ctx, raw_len):
 
 
 def test_long_keys_that_stay_apart(gpu_ctx):
+    """These keys differ and so do their hashes: they never meet in an
+    equal-hash run, and the compare's "different" verdict is not asked for.
+    Keys that differ and share their hash are in test_gpu_reduce_collisions.py."""
     x70 = b"x" * 70
     pairs = [
         (b"k" * 64 + b"a", b"k" * 64 + b"b"),  # the last raw byte

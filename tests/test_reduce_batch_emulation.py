@@ -12,8 +12,11 @@ reduce_batch_cases -- the algorithm pinned where there is no GPU:
   parse and over the segments without a final '\\n' (the line after the
   partition's lines that end before the segment's end);
 * grouping: a sort by (FNV-1a 64 of the decoded key, line); inside an
-  equal-hash run a line is dropped if an earlier line of the SAME partition has
-  the same decoded key;
+  equal-hash run a line walks back over the earlier lines and is dropped at
+  the first one of the SAME partition with the same decoded key, decided as the
+  kernels decide it: decoded length, then the escaped bytes, then the decoded
+  keys (the collide-* cases are different keys with one hash, which take the
+  walk past unequal entries and every "different" verdict);
 * an exclusive sum of the kept lengths in placed order, part_off read from it.
 
 The line language itself (go_json.parse_kv_line here) is tested elsewhere."""
@@ -32,6 +35,24 @@ def fnv64(b: bytes) -> int:
     for x in b:
         h = ((h ^ x) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
     return h
+
+
+def _escaped_equal(s: bytes, aj: int, ak: int) -> bool:
+    """the dedupe kernels' first compare: the keys' escaped bytes, from the
+    lines' starts up to the closing quote (the byte after a backslash is
+    compared and skipped, so an escaped quote does not end it)"""
+    t = 8
+    while True:
+        x = s[aj + t]
+        if x != s[ak + t]:
+            return False
+        if x == 0x22:
+            return True
+        if x == 0x5C:
+            t += 1
+            if s[aj + t] != s[ak + t]:
+                return False
+        t += 1
 
 
 def emulate(case) -> C.Expected:
@@ -78,7 +99,14 @@ def emulate(case) -> C.Expected:
         while t > 0 and h[by_hash[t - 1]] == h[j]:
             t -= 1
             k = by_hash[t]
-            if part[k] == part[j] and parsed[k][0] == parsed[j][0]:
+            if part[k] != part[j]:
+                continue  # the same key in another partition is another key
+            if len(parsed[k][0]) != len(parsed[j][0]):
+                continue
+            same = _escaped_equal(data, int(start[j]), int(start[k]))
+            if not same:  # another spelling of the same key, or another key with this hash and length
+                same = parsed[k][0] == parsed[j][0]
+            if same:
                 keep[j] = False
                 break
     # placement of the kept lines
